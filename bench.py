@@ -1,9 +1,18 @@
 #!/usr/bin/env python
 """Headline benchmark: drug-pairs/sec, fwd+bwd(+Adam), binary-DDI GGNN d=128 + Nie co-attention.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4] [--dump-outputs DIR] [--full]
     (N > 1: under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or bare: the process then
      starts that launcher itself as a child, before it has imported torch, and exits with its code)
+
+A plain run does what `value` needs and nothing else: set up, W warm-up steps, K timed steps, the outputs (--dump-outputs),
+the JSON line.  --full adds every other leg listed below (host_ms_per_step, roofline, end_to_end, batch32, predict, dedup,
+other_configs, ref_headline, cpu_baseline); in a plain run those keys are null.  --no-extras / --no-cpu-baseline drop legs
+of a --full run.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed, float32, as DIR/loss.npy (the
+step's loss, shape (1,)), DIR/grad.npy (the flat gradient of every parameter, summed over ranks) and DIR/params.npy (the flat
+parameters after the Adam update).  Store, pairs and initial weights are seeded: the same arguments give the same inputs.
 
 A "step" is one training step over one batch of 1024 drug pairs per GPU: both molecules of every pair encoded, co-attention,
 link predictor, sigmoid cross entropy, backward, one gradient all-reduce (N > 1), Adam.  Every molecule INSTANCE is encoded
@@ -18,7 +27,7 @@ Rank 0 prints ONE JSON line:
   batch32       c2 at the reference's default batch of 32 pairs (train_ddi_modify.py:196), end to end
   predict       forward only, under no-backprop: the evaluation callers' predict (eval_coattention.py:103-124)
   dedup         every distinct molecule of a step encoded once (SURVEY.md 8(d) caveat): reported beside `value`, never instead
-  other_configs the default (c2) run also times c3 and c4 for 20 steps each, with their dominant kernel's roofline fraction
+  other_configs a --full run of c2 (the default) also times c3 and c4 for 20 steps each, with their dominant kernel's roofline fraction
   ref_headline  the model the reference's published figures were trained with (DDI.md:6, RECORD.txt:246-251): GGNN hidden 32, 8
                 steps untied + Nie + NTN / HolE, at 1024 pairs (resident) and at the reference's batch of 32; fused d = 32 step
                 kernels against the unfused operator chain
@@ -203,11 +212,15 @@ def main():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the end-to-end, batch-32 and roofline legs")
+    ap.add_argument("--full", action="store_true", help="run every leg beside the timed steps (roofline, end-to-end, batch-32, "
+                                                        "predict, dedup, other configs, reference model, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, gradient and parameters as DIR/*.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the end-to-end, batch-32 and roofline legs")
     ap.add_argument("--host-profile", action="store_true", help="diagnostic: cProfile of the end-to-end epoch's host side to stderr")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
+    extras = args.full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # not under a launcher: become one (children do the work)
         raise SystemExit(self_launch(args.gpus, sys.argv[1:]))
@@ -350,15 +363,25 @@ def main():
             for i in range(warmup):
                 body(i)
             dt, every = timed(steps, lambda i: body(warmup + i))
-            loss = float(last["loss"].item())
-            # the host's own time per step: three steps issued into empty queues (nothing to wait for), untimed by the leg
+            self.last_loss = last["loss"].detach()
+            return self.gb * steps / dt, dt, every, float(last["loss"].item())
+
+        def host_ms_per_step(self):
+            """The host's own time per step: three steps issued into empty queues (nothing to wait for), after the timed
+            region of resident()."""
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(3):
-                body(i)
-            self.host_ms_per_step = round(1e3 * (time.perf_counter() - t0) / 3, 3)
+                self.train_step(*self.batches[i % len(self.batches)])
+            ms = round(1e3 * (time.perf_counter() - t0) / 3, 3)
             torch.cuda.synchronize()
-            return self.gb * steps / dt, dt, every, loss
+            return ms
+
+        def dump_outputs(self, out_dir):
+            """What the last timed step computed (module docstring, --dump-outputs)."""
+            os.makedirs(out_dir, exist_ok=True)
+            for name, t in (("loss", self.last_loss.reshape(1)), ("grad", self.opt.grad), ("params", self.opt.flat)):
+                np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
         def whole(self, value):
             return dict(alg_mflop_per_pair=round(self.alg_f / 1e6, 1), alg_kb_per_pair=round(self.alg_b / 1e3, 1),
@@ -478,12 +501,15 @@ def main():
 
     # ---- resident leg (the metric): packed batches already in HBM ---------------------------------------
     value, dt, every, loss_val = env.resident(args.steps, args.warmup)
-    env_main_host_ms = env.host_ms_per_step       # what the host needs to issue one step (measured into empty queues, outside the timed region)
+    if args.dump_outputs and rank == 0:
+        env.dump_outputs(args.dump_outputs)
+    # what the host needs to issue one step (measured into empty queues, outside the timed region)
+    env_main_host_ms = env.host_ms_per_step() if args.full else None
     rank_ms = None if world == 1 else dict(min=round(1e3 * min(every) / args.steps, 3), max=round(1e3 * max(every) / args.steps, 3))
 
     # ---- end-to-end leg: one epoch, fresh permutation, collate inside the timed region --------------------
     e2e = b32 = pred = None
-    if not args.no_extras:
+    if extras:
         host_ms = []
 
         def epoch_body(state):
@@ -558,7 +584,7 @@ def main():
 
     # ---- de-duplication leg (SURVEY.md 8(d) caveat: reported BESIDE the per-instance figure, never instead of it) ----
     dedup = None
-    if not args.no_extras and world == 1 and cfg["attn"]:
+    if extras and world == 1 and cfg["attn"]:
         nd, n_d = min(24, steps_per_epoch), 40
         dds = [env.collate(idx1, idx2, label, k, dedup=True) for k in range(nd)]
         for i in range(4):
@@ -582,11 +608,11 @@ def main():
 
     # ---- roofline leg: HIP events around every launch (all classes), same workload, rank 0 -------------------
     whole = env.whole(value) if rank == 0 else None
-    roof = env.roofline() if (rank == 0 and not args.no_extras) else None
+    roof = env.roofline() if (rank == 0 and extras) else None
 
     # ---- the other single-GPU configurations of BASELINE.json, where the driver sees them (default run only) ----
     others = None
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "c2" and os.environ.get("BMP_BENCH_OTHERS", "1") != "0":
+    if rank == 0 and world == 1 and extras and args.config == "c2" and os.environ.get("BMP_BENCH_OTHERS", "1") != "0":
         others = {}
         del batches
         for name in ("c3", "c4"):
@@ -594,9 +620,10 @@ def main():
             torch.cuda.empty_cache()
             e = Env(name, n_batches=24)
             v, dt_o, _, loss_o = e.resident(20, 4)
+            host_ms_o = e.host_ms_per_step()
             r = e.roofline()
             others[name] = dict(value=round(v, 1), unit="pairs/s", ms_per_step=round(1e3 * dt_o / 20, 3), steps=20, warmup=4,
-                                host_ms_per_step=e.host_ms_per_step,
+                                host_ms_per_step=host_ms_o,
                                 whole_step=e.whole(v), loss=round(loss_o, 5), workload=e.cfg["workload"],
                                 dominant_kernel=None if r is None else dict(kernel=r["kernel"], frac=r["frac"], achieved=r["achieved"],
                                                                             avg_launch_us=r["avg_launch_us"], traffic=r["traffic"],
@@ -607,7 +634,7 @@ def main():
     # ---- the reference's PUBLISHED model (DDI.md:6, RECORD.txt:246-251; train_binary.py:165-187,226-227): GGNN hidden 32, 8
     #      steps, untied, fp_out 16 + Nie + NTN / HolE without hidden layers, at the reference's batch of 32 and at 1024 pairs ----
     ref_head = None
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "c2" and os.environ.get("BMP_BENCH_REF", "1") != "0":
+    if rank == 0 and world == 1 and extras and args.config == "c2" and os.environ.get("BMP_BENCH_REF", "1") != "0":
         ref_head = {}
         for name in ("ref_ntn", "ref_hole"):
             torch.cuda.empty_cache()
@@ -647,7 +674,7 @@ def main():
             del e
 
     cpu = cpu_more = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, cpu_more = cpu_baseline(cfg, store, idx1, idx2, label)
 
     if rank == 0:

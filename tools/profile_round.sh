@@ -38,8 +38,8 @@ rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ks_ref -- $B 
 python tools/summarize_prof.py gpurun_out/ks_ref gpurun_out/${R}_ref_ntn_kernel_stats.csv 34 > /dev/null
 rm -rf gpurun_out/ks_ref
 unset BMP_ONE_STREAM
-python bench.py > gpurun_out/${R}_bench_c2.json 2> gpurun_out/${R}_bench_c2.err
+python bench.py --full > profiles/${R}_bench_c2.json 2> profiles/${R}_bench_c2.err
 for c in c3 c4; do
-  python bench.py --config $c --no-cpu-baseline > gpurun_out/${R}_bench_$c.json 2> gpurun_out/${R}_bench_$c.err
+  python bench.py --full --config $c --no-cpu-baseline > profiles/${R}_bench_$c.json 2> profiles/${R}_bench_$c.err
 done
-ls gpurun_out | grep ${R}_bench
+ls profiles | grep ${R}_bench
