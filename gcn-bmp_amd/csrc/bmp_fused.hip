@@ -11,7 +11,6 @@
 //   wave (wr, wc) owns rows [wr*RB*32, +RB*32) x cols [wc*32, +32) of every [128 x D] result,
 //   D = 128: 2 x 4 waves, RB = 2;  D = 64: 4 x 2 waves, RB = 1.
 //   dense work: v_mfma_f32_32x32x2_f32 (exact f32); K order per lane: four consecutive k per 16-B read.
-#include <stdlib.h>
 #include <type_traits>
 #include <string.h>
 #include "bmp_kernels.h"
@@ -823,26 +822,24 @@ static int step_wgrad_problems(WGArgs* g, const float* h, const float* m, const 
 static bool step_wgrad_fusable(int N, int d) { return (d == 64 || d == 128) && (N & 31) == 0; }
 // Will bmp_ggnn_step_wgrad / bmp_relgcn_layer_wgrad, handed row lists, read gda's per-type blocks through them (and through
 // them only)?  The caller's licence for skip_zero_g of the backward launches.
-extern "C" int bmp_step_wgrad_lists_used(int N, int d) {
-    static const bool unfused = getenv("BMP_STEP_WGRAD_UNFUSED") != nullptr;
-    return !unfused && step_wgrad_fusable(N, d) && bmp_wgrad_fused_lists_ok(N);
-}
+extern "C" int bmp_step_wgrad_lists_used(int N, int d) { return step_wgrad_fusable(N, d) && bmp_wgrad_fused_lists_ok(N); }
 
 extern "C" size_t bmp_ggnn_step_wgrad_ws_floats(int N, int d) {
-    size_t a = bmp_wgrad_ws_floats(N, d, 7 * d);
-    if (d == 32 && (N & 7) == 0) { const size_t b = bmp_step_wgrad_small_ws_floats(N, d); if (b > a) a = b; }
+    size_t a = 0;
+    if (d == 32 && (N & 7) == 0) a = bmp_step_wgrad_small_ws_floats(N, d);
     if (step_wgrad_fusable(N, d)) {
-        WGArgs g[BMP_WG_MAXP];
-        int n = step_wgrad_problems(g, nullptr, nullptr, nullptr, nullptr, N, d, 0, nullptr, nullptr, nullptr, (float*)16, 0);
-        size_t b = bmp_wgrad_fused_ws_floats(g, n);
-        if (b > a) a = b;
-        n = step_wgrad_problems(g, nullptr, nullptr, nullptr, nullptr, N, d, 0, nullptr, nullptr, nullptr, (float*)16, 0, (const int*)16, (const int*)16);
-        b = bmp_wgrad_fused_ws_floats(g, n);
-        if (b > a) a = b;
-        n = step_wgrad_problems(g, nullptr, nullptr, nullptr, nullptr, N, d, 0, nullptr, nullptr, nullptr, (float*)16, 0, (const int*)16, (const int*)16,
-                                (const int*)16, (const int*)16);
-        b = bmp_wgrad_fused_ws_floats(g, n);
-        if (b > a) a = b;
+        // every problem set the call can build: first or later call (the first call's narrower problems take more row
+        // splits each), without row lists, with the type lists, with the type and the live lists
+        const int* l = (const int*)16;
+        for (int first = 0; first < 2; ++first)
+            for (int lists = 0; lists < 3; ++lists) {
+                WGArgs g[BMP_WG_MAXP];
+                const int n = step_wgrad_problems(g, nullptr, nullptr, nullptr, nullptr, N, d, first, nullptr, nullptr, nullptr, (float*)16, 0,
+                                                  lists > 0 ? l : nullptr, lists > 0 ? l : nullptr, lists > 1 ? l : nullptr,
+                                                  lists > 1 ? l : nullptr);
+                const size_t b = bmp_wgrad_fused_ws_floats(g, n);
+                if (b > a) a = b;
+            }
     }
     return a;
 }
@@ -856,6 +853,8 @@ extern "C" size_t bmp_ggnn_step_wgrad_ws_floats(int N, int d) {
 // first != 0: the da_r columns of gda are not read (bmp_ggnn_step_bwd does not write them) and count as zeros.
 // type_rows / type_cnt: optional row lists of the batch's TRANSPOSED CSR (bmp_type_rows): the per-type blocks then sum over
 // the rows that have a bond of the type only (the others' G_e rows are exact zeros: same sums, fewer products).
+// d = 32 needs N a multiple of 8 and gda 16-byte aligned; d = 64 / 128 need N a multiple of 32 and h, m, rz, gda 16-byte
+// aligned.  Anything else is an error: there is no second path that would read the blocks a skip_zero_g backward left unwritten.
 extern "C" int bmp_ggnn_step_wgrad(const float* h, const float* m, const float* rz, const float* gda, int N, int d,
                                    int first, float* o1, float* o2, float* dUcT, float* cs, int accumulate,
                                    const int* type_rows, const int* type_cnt, const int* live_rows, const int* live_cnt,
@@ -863,33 +862,17 @@ extern "C" int bmp_ggnn_step_wgrad(const float* h, const float* m, const float* 
     BMP_REQUIRE(N > 0 && d > 0 && ws_floats >= bmp_ggnn_step_wgrad_ws_floats(N, d));
     BMP_REQUIRE((live_rows != nullptr) == (live_cnt != nullptr));
     BMP_REQUIRE(h && m && rz && gda && o1 && o2 && dUcT && cs && ws);
-    static const bool unfused = getenv("BMP_STEP_WGRAD_UNFUSED") != nullptr;        // A/B switch (tools, tests)
-    if (!unfused && d == 32 && (N & 7) == 0 && ((uintptr_t)gda & 15) == 0)          // one 32-row MFMA block per output: bmp_fused_small.hip
+    if (d == 32) {          // one 32-row MFMA block per output: bmp_fused_small.hip
+        BMP_REQUIRE((N & 7) == 0 && ((uintptr_t)gda & 15) == 0);
         return bmp_launch_step_wgrad_small(h, m, rz, gda, N, d, first, o1, o2, dUcT, cs, accumulate, ws, st);
-    if (!unfused && step_wgrad_fusable(N, d) && ((uintptr_t)h & 15) == 0 && ((uintptr_t)m & 15) == 0 && ((uintptr_t)rz & 15) == 0 &&
-        ((uintptr_t)gda & 15) == 0) {
-        WGArgs g[BMP_WG_MAXP];
-        const bool lists = type_rows != nullptr && type_cnt != nullptr && bmp_wgrad_fused_lists_ok(N);
-        const int n = step_wgrad_problems(g, h, m, rz, gda, N, d, first, o1, o2, dUcT, cs, accumulate, lists ? type_rows : nullptr,
-                                          lists ? type_cnt : nullptr, lists ? live_rows : nullptr, lists ? live_cnt : nullptr);
-        return bmp_launch_wgrad_fused(g, n, ws, st, BMP_KID_WGRAD_STEP);
     }
-    // one launch per product (first steps: the da_r columns of gda are not written, so they are zeroed here first)
-    int rc;
-    if (first) {
-        hipError_t e = hipMemset2DAsync(const_cast<float*>(gda) + 4 * d, (size_t)7 * d * sizeof(float), 0, (size_t)d * sizeof(float), N, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    WGArgs g1{h, nullptr, d, 0, gda, 7 * d, d, 7 * d, N, o1, 7 * d, accumulate, cs};     // + column sums of gda
-    if ((rc = bmp_launch_wgrad(g1, ws, st))) return rc;
-    WGArgs g2{m, nullptr, d, 0, gda + 4 * d, 7 * d, d, 3 * d, N, o2, 3 * d, accumulate};
-    if ((rc = bmp_launch_wgrad(g2, ws, st))) return rc;
-    if (first) {
-        if (!accumulate) { hipError_t e = hipMemsetAsync(dUcT, 0, (size_t)d * d * sizeof(float), st); if (e != hipSuccess) return (int)e; }
-        return 0;
-    }
-    WGArgs g3{rz, h, 2 * d, d, gda + 6 * d, 7 * d, d, d, N, dUcT, d, accumulate};
-    return bmp_launch_wgrad(g3, ws, st);
+    BMP_REQUIRE(step_wgrad_fusable(N, d) && ((uintptr_t)h & 15) == 0 && ((uintptr_t)m & 15) == 0 && ((uintptr_t)rz & 15) == 0 &&
+                ((uintptr_t)gda & 15) == 0);
+    WGArgs g[BMP_WG_MAXP];
+    const bool lists = type_rows != nullptr && type_cnt != nullptr && bmp_wgrad_fused_lists_ok(N);
+    const int n = step_wgrad_problems(g, h, m, rz, gda, N, d, first, o1, o2, dUcT, cs, accumulate, lists ? type_rows : nullptr,
+                                      lists ? type_cnt : nullptr, lists ? live_rows : nullptr, lists ? live_cnt : nullptr);
+    return bmp_launch_wgrad_fused(g, n, ws, st, BMP_KID_WGRAD_STEP);
 }
 
 // ---- fused RelGCN layer (d_in == d_out in {64, 128}) ----
@@ -953,15 +936,13 @@ static int rel_wgrad_problem(WGArgs* g, const float* h, const float* wdeg, const
 }
 
 extern "C" size_t bmp_relgcn_layer_wgrad_ws_floats(int N, int d) {
-    size_t a = bmp_wgrad_ws_floats(N, d, 5 * d), b = bmp_wgrad_ws_floats(N, 4, d);
-    a = a > b ? a : b;
+    size_t a = 0;
     if (step_wgrad_fusable(N, d)) {
         WGArgs g[BMP_WG_MAXP];
         int n = rel_wgrad_problem(g, nullptr, (const float*)16, nullptr, N, d, nullptr, (float*)16, (float*)16, 0);
-        b = bmp_wgrad_fused_ws_floats(g, n);
-        if (b > a) a = b;
+        a = bmp_wgrad_fused_ws_floats(g, n);
         n = rel_wgrad_problem(g, nullptr, (const float*)16, nullptr, N, d, nullptr, (float*)16, (float*)16, 0, (const int*)16, (const int*)16);
-        b = bmp_wgrad_fused_ws_floats(g, n);
+        const size_t b = bmp_wgrad_fused_ws_floats(g, n);
         if (b > a) a = b;
     }
     return a;
@@ -971,23 +952,17 @@ extern "C" size_t bmp_relgcn_layer_wgrad_ws_floats(int N, int d) {
 //   o1 [d x 5d] = h^T . gda     cols [0,4d): dWT as [k][e*d + c];  cols [4d,5d): dWsT
 //   dbE [4 x d] = wdeg^T . dpre (weighted column sums of the dpre tile, carried by the same launch)
 //   cs [5d]     = column sums of gda; cs[4d:] = dbs
+// d = 64 / 128, N a multiple of 32 and h, wdeg, gda 16-byte aligned; anything else is an error (see bmp_ggnn_step_wgrad).
 extern "C" int bmp_relgcn_layer_wgrad(const float* h, const float* wdeg, const float* gda, int N, int d, float* o1, float* dbE,
                                       float* cs, int accumulate, const int* type_rows, const int* type_cnt, float* ws, size_t ws_floats,
                                       hipStream_t st) {
     BMP_REQUIRE(N > 0 && d > 0 && ws_floats >= bmp_relgcn_layer_wgrad_ws_floats(N, d));
     BMP_REQUIRE(h && wdeg && gda && o1 && dbE && cs && ws);
-    static const bool unfused = getenv("BMP_STEP_WGRAD_UNFUSED") != nullptr;        // A/B switch (tools, tests)
-    if (!unfused && step_wgrad_fusable(N, d) && ((uintptr_t)h & 15) == 0 && ((uintptr_t)gda & 15) == 0 && ((uintptr_t)wdeg & 15) == 0) {
-        WGArgs g[BMP_WG_MAXP];
-        const bool lists = type_rows != nullptr && type_cnt != nullptr && bmp_wgrad_fused_lists_ok(N);
-        const int n = rel_wgrad_problem(g, h, wdeg, gda, N, d, o1, dbE, cs, accumulate, lists ? type_rows : nullptr, lists ? type_cnt : nullptr);
-        return bmp_launch_wgrad_fused(g, n, ws, st, BMP_KID_WGRAD_STEP);
-    }
-    int rc;
-    WGArgs g1{h, nullptr, d, 0, gda, 5 * d, d, 5 * d, N, o1, 5 * d, accumulate, cs};
-    if ((rc = bmp_launch_wgrad(g1, ws, st))) return rc;
-    WGArgs g2{wdeg, nullptr, 4, 0, gda + 4 * d, 5 * d, 4, d, N, dbE, d, accumulate};
-    return bmp_launch_wgrad(g2, ws, st);
+    BMP_REQUIRE(step_wgrad_fusable(N, d) && ((uintptr_t)h & 15) == 0 && ((uintptr_t)gda & 15) == 0 && ((uintptr_t)wdeg & 15) == 0);
+    WGArgs g[BMP_WG_MAXP];
+    const bool lists = type_rows != nullptr && type_cnt != nullptr && bmp_wgrad_fused_lists_ok(N);
+    const int n = rel_wgrad_problem(g, h, wdeg, gda, N, d, o1, dbE, cs, accumulate, lists ? type_rows : nullptr, lists ? type_cnt : nullptr);
+    return bmp_launch_wgrad_fused(g, n, ws, st, BMP_KID_WGRAD_STEP);
 }
 
 // ---- readout forward on the tile machinery (d == o in {64, 128}; h0 absent or d wide) ----

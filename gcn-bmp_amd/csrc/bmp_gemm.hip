@@ -1,6 +1,5 @@
 // fp32-MFMA GEMM building blocks for gfx950: the row GEMM (atom-row tiles x weights) and the
 // weight-gradient GEMM (reduction over atom rows).  See bmp_kernels.h for the contracts.
-#include <stdlib.h>
 #include <string.h>
 #include "bmp_kernels.h"
 
@@ -286,127 +285,12 @@ __device__ __forceinline__ void rowgemm_body(const RGArgs& a, int bx, int by, fl
 // Row GEMM, both operands through LDS: 128 rows x 128 columns per workgroup (4 waves, each all 128 rows x 32 columns).
 // The direct form above reads its weight fragments straight from L2 one k-step ahead; vmcnt retires in order, so that
 // read queues behind the NEXT chunk's row loads (HBM latency) at every chunk start and the matrix pipe waits
-// (SQ_WAIT_INST_ANY: half of the wave cycles, MFMA busy 0.38 on the readout GEMM).  Here a 64-deep chunk of the rows AND
-// of the weights is requested at the top of the previous chunk, lands during its MFMAs and is written to LDS at the
-// chunk boundary; inside a chunk the waves only wait on LDS.  Needs Nout, ldw multiples of 4 and 16-byte aligned weights.
-// ---------------------------------------------------------------------------------------------
-#define RGB_LDB 132
-template <int EPI>
-__device__ __forceinline__ void rowgemm_lds_body(const RGArgs& a, int bx, int by, float* lds) {
-    constexpr int RB = 4, R = 128, NT = 128;
-    float* la = lds;                         // [128][BMP_LDS_LD]  rows x k
-    float* lb = lds + R * BMP_LDS_LD;        // [64][RGB_LDB]      k x columns
-    const int tid = threadIdx.x, lane = tid & 63, wc = tid >> 6;
-    const int l31 = lane & 31, hi = lane >> 5;
-    const int row0 = bx * R, n0 = by * NT;
-
-    f32x16 acc[RB];
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[rb][i] = 0.f;
-
-    f32x4 sa[8], sb[8];                      // the chunk in flight: 128 x 64 rows, 64 x 128 weights
-    const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto load_chunk = [&](int s_, int k0_) {
-        const float* __restrict__ X = a.s[s_].X;
-        const float* __restrict__ X2 = a.s[s_].X2;
-        const float* __restrict__ Wt = a.s[s_].Wt;
-        const int ldx = a.s[s_].ldx, ldx2 = a.s[s_].ldx2, ldw = a.s[s_].ldw, K = a.s[s_].K;
-        const int kc = (K - k0_) < 64 ? (K - k0_) : 64;
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int idx = tid + it * 256;
-            const int r = idx >> 4, c4 = idx & 15;
-            f32x4 v = zero4;
-            if (4 * c4 < kc) {
-                v = *(const f32x4*)(X + (size_t)(row0 + r) * ldx + k0_ + 4 * c4);
-                if (X2) v *= *(const f32x4*)(X2 + (size_t)(row0 + r) * ldx2 + k0_ + 4 * c4);
-            }
-            sa[it] = v;
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int idx = tid + it * 256;
-            const int k = idx >> 5, c4 = idx & 31;
-            const int col = n0 + 4 * c4;
-            sb[it] = (k < kc && col < a.Nout) ? *(const f32x4*)(Wt + (size_t)(k0_ + k) * ldw + col) : zero4;
-        }
-    };
-    auto store_chunk = [&]() {
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int idx = tid + it * 256;
-            *(f32x4*)(&la[(idx >> 4) * BMP_LDS_LD + 4 * (idx & 15)]) = sa[it];
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int idx = tid + it * 256;
-            *(f32x4*)(&lb[(idx >> 5) * RGB_LDB + 4 * (idx & 31)]) = sb[it];
-        }
-    };
-    load_chunk(0, 0);
-    store_chunk();
-    __syncthreads();
-    for (int s = 0; s < a.nsrc; ++s) {
-        const int K = a.s[s].K;
-        for (int k0 = 0; k0 < K; k0 += 64) {
-            const int kc = (K - k0) < 64 ? (K - k0) : 64;
-            int cs = s, ck0 = k0 + 64;
-            if (ck0 >= K) { cs = s + 1; ck0 = 0; }
-            const bool more = cs < a.nsrc;
-            if (more) load_chunk(cs, ck0);
-            f32x4 a0[RB], a1[RB];
-            float b0[4], b1[4];
-#pragma unroll
-            for (int rb = 0; rb < RB; ++rb) a0[rb] = *(const f32x4*)(&la[(rb * 32 + l31) * BMP_LDS_LD + 4 * hi]);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) b0[t] = lb[(4 * hi + t) * RGB_LDB + wc * 32 + l31];
-            for (int kk = 0; kk < kc; kk += 8) {
-                if (kk + 8 < kc) {
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) b1[t] = lb[(kk + 8 + 4 * hi + t) * RGB_LDB + wc * 32 + l31];
-#pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) a1[rb] = *(const f32x4*)(&la[(rb * 32 + l31) * BMP_LDS_LD + kk + 8 + 4 * hi]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int rb = 0; rb < RB; ++rb) acc[rb] = bmp_mfma(a0[rb][t], b0[t], acc[rb]);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int rb = 0; rb < RB; ++rb) a0[rb] = a1[rb];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) b0[t] = b1[t];
-            }
-            if (more) {
-                __syncthreads();
-                store_chunk();
-                __syncthreads();
-            }
-        }
-    }
-    const int col = n0 + wc * 32 + l31;
-    if (col < a.Nout) {
-        const RGCol cc = rg_col(a, col);
-#pragma unroll
-        for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = row0 + rb * 32 + bmp_acc_row(reg, lane);
-                rg_epilogue<EPI>(a, cc, row, col, acc[rb][reg]);
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same 128 x 128 tile with both operands DOUBLE-buffered in LDS in 32-deep K chunks: chunk c + 1 is requested into
-// registers at the top of chunk c and written to the other buffer after its MFMAs -- one barrier per chunk instead of a
-// store between two barriers with the matrix pipe idle; the weights sit in LDS as [k/4][column][4] (16-byte slot of column
-// n at n ^ ((n >> 4) & 3): the register-transposing store and the fragment reads are both bank-conflict free), so a
-// lane's four consecutive k of its column are ONE ds_read_b128 (the form above reads four ds_read_b32).  Same LDS
-// footprint (two workgroups per CU), same epilogue.
+// (SQ_WAIT_INST_ANY: half of the wave cycles, MFMA busy 0.38 on the readout GEMM).  Here both operands are DOUBLE-buffered
+// in LDS in 32-deep K chunks: chunk c + 1 is requested into registers at the top of chunk c and written to the other
+// buffer after its MFMAs -- one barrier per chunk; inside a chunk the waves only wait on LDS.  The weights sit in LDS as
+// [k/4][column][4] (16-byte slot of column n at n ^ ((n >> 4) & 3): the register-transposing store and the fragment reads
+// are both bank-conflict free), so a lane's four consecutive k of its column are ONE ds_read_b128.  Two workgroups per CU.
+// Needs Nout, ldw multiples of 4 and 16-byte aligned weights (rowgemm_db_ok).
 // ---------------------------------------------------------------------------------------------
 #define RGD_LDA 36
 #define RGD_A_FLOATS (128 * RGD_LDA)
@@ -565,15 +449,8 @@ __global__ __launch_bounds__(256) void k_rowgemm_db_listed(RGArgs a) {
     rowgemm_db_body<BMP_EPI_GENERIC, true>(a, blockIdx.x, blockIdx.y, lds, rows);
 }
 
-template <int EPI>
-__global__ __launch_bounds__(256) void k_rowgemm_lds(RGArgs a) {
-    __shared__ __attribute__((aligned(16))) float lds[128 * BMP_LDS_LD + 64 * RGB_LDB];
-    rowgemm_lds_body<EPI>(a, blockIdx.x, blockIdx.y, lds);
-}
-
-static bool rowgemm_lds_ok(const RGArgs& a) {
-    static const bool off = getenv("BMP_ROWGEMM_DIRECT") != nullptr;      // tests compare the two forms
-    if (off) return false;
+// the weights k_rowgemm_db / k_rowgemm_db_listed can stage: 16-byte pieces
+static bool rowgemm_db_ok(const RGArgs& a) {
     if ((a.Nout & 3) != 0) return false;
     for (int s = 0; s < a.nsrc; ++s)
         if ((a.s[s].ldw & 3) != 0 || ((uintptr_t)a.s[s].Wt & 15) != 0) return false;
@@ -609,15 +486,10 @@ __global__ __launch_bounds__(256) void k_rowgemm_multi(RGMulti m) {
     else rowgemm_body<1, 2, 1, BMP_EPI_GENERIC>(m.p[p], bx - m.bx0[p], blockIdx.y, lds);      // 64-row workgroups: two per tile
 }
 
-static bool rg_scalar_epilogue() {
-    static const bool on = getenv("BMP_ROWGEMM_SCALAR_EPI") != nullptr;      // A/B: the accumulator-layout epilogue everywhere
-    return on;
-}
-
 template <int EPI>
 static int launch_rowgemm_epi(const RGArgs& a_, int n_tiles, hipStream_t st) {
     RGArgs a = a_;
-    a.vec_epi = !rg_scalar_epilogue() && rg_vec_ok(a_, EPI);       // (k_rowgemm_lds keeps the accumulator-layout form)
+    a.vec_epi = rg_vec_ok(a_, EPI);
     if (a.Nout <= 32) {
         hipLaunchKernelGGL((k_rowgemm<4, 1, 1, EPI>), dim3(n_tiles, 1), dim3(256), 0, st, a);
     } else if (a.Nout <= 64) {
@@ -625,12 +497,10 @@ static int launch_rowgemm_epi(const RGArgs& a_, int n_tiles, hipStream_t st) {
     } else {
         const int ny = (a.Nout + 127) / 128;
         // problems that do not even give every CU one 128-row workgroup take 64-row workgroups: the launch is one
-        // round either way, and its duration is one workgroup's latency
-        static const int form = getenv("BMP_ROWGEMM_FORM") ? atoi(getenv("BMP_ROWGEMM_FORM")) : 0;    // 1: single-buffered form
-        if (n_tiles * ny <= 256) hipLaunchKernelGGL((k_rowgemm<1, 2, 1, EPI>), dim3(2 * n_tiles, ny), dim3(256), 0, st, a);
-        else if (rowgemm_lds_ok(a) && form != 1) hipLaunchKernelGGL((k_rowgemm_db<EPI>), dim3(n_tiles, ny), dim3(256), 0, st, a);
-        else if (rowgemm_lds_ok(a)) hipLaunchKernelGGL((k_rowgemm_lds<EPI>), dim3(n_tiles, ny), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_rowgemm<1, 4, 1, EPI>), dim3(n_tiles, ny), dim3(256), 0, st, a);
+        // round either way, and its duration is one workgroup's latency; weights the LDS-staged kernel cannot stage
+        // (misaligned, or Nout not a multiple of 4) take the same 64-row form
+        if (n_tiles * ny > 256 && rowgemm_db_ok(a)) hipLaunchKernelGGL((k_rowgemm_db<EPI>), dim3(n_tiles, ny), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_rowgemm<1, 2, 1, EPI>), dim3(2 * n_tiles, ny), dim3(256), 0, st, a);
     }
     BMP_LAUNCH_CHECK();
     return 0;
@@ -655,10 +525,10 @@ int bmp_launch_rowgemm(const RGArgs& a, int n_tiles, int epi, hipStream_t st) {
     return -1;
 }
 
-bool bmp_rowgemm_listed_ok(const RGArgs& a) { return a.ridx && a.rcnt && rowgemm_lds_ok(a); }
+bool bmp_rowgemm_listed_ok(const RGArgs& a) { return a.ridx && a.rcnt && rowgemm_db_ok(a); }
 
 int bmp_launch_rowgemm_listed(const RGArgs& a, int n_tiles_cap, hipStream_t st) {
-    BMP_REQUIRE(n_tiles_cap > 0 && a.Nout > 0 && a.nsrc >= 1 && a.nsrc <= 3 && a.ridx && a.rcnt && rowgemm_lds_ok(a));
+    BMP_REQUIRE(n_tiles_cap > 0 && a.Nout > 0 && a.nsrc >= 1 && a.nsrc <= 3 && a.ridx && a.rcnt && rowgemm_db_ok(a));
     double ksum = 0;
     for (int s = 0; s < a.nsrc; ++s) {
         BMP_REQUIRE(a.s[s].K > 0 && (a.s[s].K & 7) == 0 && (a.s[s].ldx & 3) == 0 && ((uintptr_t)a.s[s].X & 15) == 0 && !a.s[s].X2);
@@ -668,7 +538,7 @@ int bmp_launch_rowgemm_listed(const RGArgs& a, int n_tiles_cap, hipStream_t st) 
     const double rows = (double)n_tiles_cap * BMP_R;
     BmpProfScope prof(BMP_KCLS_ROWGEMM, 2.0 * rows * ksum * a.Nout, 4.0 * rows * (ksum + a.Nout), st);
     RGArgs b = a;
-    b.vec_epi = !rg_scalar_epilogue() && rg_vec_ok(a, BMP_EPI_GENERIC);
+    b.vec_epi = rg_vec_ok(a, BMP_EPI_GENERIC);
     hipLaunchKernelGGL(k_rowgemm_db_listed, dim3(n_tiles_cap, (a.Nout + 127) / 128), dim3(256), 0, st, b);
     BMP_LAUNCH_CHECK();
     return 0;
@@ -676,7 +546,6 @@ int bmp_launch_rowgemm_listed(const RGArgs& a, int n_tiles_cap, hipStream_t st) 
 
 int bmp_launch_rowgemm_multi(const RGArgs* a, const int* n_tiles, int n, hipStream_t st) {
     BMP_REQUIRE(n >= 1 && n <= 3);
-    static const bool no_thin = getenv("BMP_ROWGEMM_NO_THIN") != nullptr;       // A/B: the remainder as a second column tile
     RGMulti m; memset(&m, 0, sizeof(m));
     int np = 0, nymax = 1;
     int nt_of[RGM_MAXP];
@@ -694,7 +563,7 @@ int bmp_launch_rowgemm_multi(const RGArgs* a, const int* n_tiles, int n, hipStre
         const int rem = a[p].Nout & 127;
         const bool plain = a[p].split <= 0 && !a[p].add && !a[p].wdeg && !a[p].o1 && !a[p].ridx;
         m.p[np] = a[p]; nt_of[np] = n_tiles[p];
-        if (!no_thin && plain && a[p].Nout > 128 && rem >= 1 && rem <= 32) m.p[np].Nout = a[p].Nout - rem;
+        if (plain && a[p].Nout > 128 && rem >= 1 && rem <= 32) m.p[np].Nout = a[p].Nout - rem;
         m.ny[np] = (m.p[np].Nout + 127) / 128;
         if (m.ny[np] > nymax) nymax = m.ny[np];
         ++np;
@@ -710,7 +579,7 @@ int bmp_launch_rowgemm_multi(const RGArgs* a, const int* n_tiles, int n, hipStre
         ++np;
     }
     int blocks = 0;
-    for (int q = 0; q < np; ++q) m.p[q].vec_epi = !rg_scalar_epilogue() && rg_vec_ok(m.p[q], BMP_EPI_GENERIC);
+    for (int q = 0; q < np; ++q) m.p[q].vec_epi = rg_vec_ok(m.p[q], BMP_EPI_GENERIC);
     for (int q = 0; q < np; ++q) { m.bx0[q] = blocks; blocks += 2 * nt_of[q]; }
     for (int q = np; q <= RGM_MAXP; ++q) m.bx0[q] = blocks;
     for (int q = np; q < RGM_MAXP; ++q) m.bx0[q] = 0x7fffffff;      // (the kernel's search never lands behind the last problem)
@@ -1219,12 +1088,12 @@ __device__ __forceinline__ int wgk_problem(const WGKMulti& m, int by) {
     for (int q = 1; q < BMP_WG_MAXP; ++q) p += (q < m.n && by >= m.ty0[q]) ? 1 : 0;
     return p;
 }
-// STEP = 1: the launch of bmp_launch_wgrad_fused (same code; a separate symbol so that profiles tell the fused step
-// weight gradients from the co-attention's small three-problem launch)
+// Up to BMP_WG_MAXP weight-gradient problems in one launch on the LDS-DMA body (wgrad_dma_body); m.ssz = floats of one stage
+// in the dynamic LDS block.  STEP = 1: the launch of bmp_launch_wgrad_fused (same code; a separate symbol so that profiles
+// tell the fused step weight gradients from the co-attention's small three-problem launch)
 template <int STEP>
-__global__ __launch_bounds__(256) void k_wgrad_lds_multi(WGKMulti m) {
-    __shared__ __attribute__((aligned(16))) float XS[2][32][WG_LD];
-    __shared__ __attribute__((aligned(16))) float YS[2][32][WG_LD];
+__global__ __launch_bounds__(256) void k_wgrad_dma_multi(WGKMulti m) {
+    extern __shared__ __attribute__((aligned(16))) float wd_sm[];
     int by, bz;
     if (m.grouped == 2) { if (!wgk_flat(m, blockIdx.x, by, bz)) return; }
     else if (m.grouped) {
@@ -1244,51 +1113,20 @@ __global__ __launch_bounds__(256) void k_wgrad_lds_multi(WGKMulti m) {
     } else { by = blockIdx.y; bz = blockIdx.z; }
     const int p = wgk_problem(m, by);
     if (bz >= m.S[p]) return;
-    if (m.p[p].X2) wgrad_lds_body<true>(m.p[p], m.want_cs[p], 0, by - m.ty0[p], bz, XS, YS);
-    else wgrad_lds_body<false>(m.p[p], m.want_cs[p], 0, by - m.ty0[p], bz, XS, YS);
-}
-
-// The same launch on the LDS-DMA body (wgrad_dma_body); m.ssz = floats of one stage in the dynamic LDS block.
-template <int STEP>
-__global__ __launch_bounds__(256) void k_wgrad_dma_multi(WGKMulti m) {
-    extern __shared__ __attribute__((aligned(16))) float wd_sm[];
-    int by, bz;
-    if (m.grouped == 2) { if (!wgk_flat(m, blockIdx.x, by, bz)) return; }
-    else if (m.grouped) {     // see k_wgrad_lds_multi
-        const int T = m.ty0[BMP_WG_MAXP], L = blockIdx.x, xcd = L & 7, slot = L >> 3, G = m.smax >> 3;
-        if (slot < G * T) { bz = xcd * G + slot / T; by = slot % T; }
-        else {
-            const int r = (slot - G * T) * 8 + xcd;
-            if (r >= (m.smax - 8 * G) * T) return;
-            bz = 8 * G + r / T; by = r % T;
-        }
-    } else { by = blockIdx.y; bz = blockIdx.z; }
-    const int p = wgk_problem(m, by);
-    if (bz >= m.S[p]) return;
     if (m.p[p].ridx) wgrad_dma_body<false, true>(m.p[p], m.want_cs[p], 0, by - m.ty0[p], bz, wd_sm, m.ssz);
     else if (m.p[p].X2) wgrad_dma_body<true, false>(m.p[p], m.want_cs[p], 0, by - m.ty0[p], bz, wd_sm, m.ssz);
     else wgrad_dma_body<false, false>(m.p[p], m.want_cs[p], 0, by - m.ty0[p], bz, wd_sm, m.ssz);
 }
 
-// Launches k_wgrad_dma_multi<STEP> when every problem of the launch can take the DMA body (whole 16-byte pieces in range:
-// K and Nn at least 4 and multiples of 4 -- wgrad_use_lds --, no one-hot operand), else k_wgrad_lds_multi<STEP>.
-// BMP_WGRAD_DMA=0: always the register-staged kernel.
-static bool wgrad_dma_enabled() {
-    static const int on = [] { const char* e = getenv("BMP_WGRAD_DMA"); return e ? atoi(e) : 1; }();
-    return on != 0;
-}
+// Launches k_wgrad_dma_multi<STEP>.  Every problem with work needs the DMA body's whole 16-byte pieces in range: K and Nn at
+// least 4 and multiples of 4 (wgrad_use_lds), no one-hot operand, rows in whole stages.
 template <int STEP>
 static int wgrad_multi_launch(WGKMulti& m, int n, const dim3& grid, hipStream_t st) {
-    bool ok = wgrad_dma_enabled(), x2 = false;
+    bool x2 = false;
     for (int p = 0; p < n; ++p) {
         if (m.S[p] == 0) continue;
-        ok = ok && !m.p[p].onehot && m.p[p].K >= 4 && m.p[p].Nn >= 4 && (m.p[p].rows_per_split % WD_RS) == 0 && (m.p[p].N % WD_RS) == 0;
+        BMP_REQUIRE(!m.p[p].onehot && m.p[p].K >= 4 && m.p[p].Nn >= 4 && (m.p[p].rows_per_split % WD_RS) == 0 && (m.p[p].N % WD_RS) == 0);
         x2 = x2 || m.p[p].X2 != nullptr;
-    }
-    if (!ok) {
-        for (int p = 0; p < n; ++p) BMP_REQUIRE(m.p[p].ridx == nullptr);       // row lists exist in the LDS-DMA body only
-        hipLaunchKernelGGL((k_wgrad_lds_multi<STEP>), grid, dim3(256), 0, st, m);
-        return 0;
     }
     m.ssz = WD_RS * 128 * (x2 ? 3 : 2) + WD_RS * 4;          // + the rows' four weights
     const size_t lds = (size_t)WD_NS * m.ssz * sizeof(float);
@@ -1298,9 +1136,8 @@ static int wgrad_multi_launch(WGKMulti& m, int n, const dim3& grid, hipStream_t 
 }
 
 // Grid of a three-problem launch: XCD-grouped (see the kernel) when the work fits the chip's 512 slots in one round and there
-// is more than one column tile to share operands; else the plain (tile, split) grid.  BMP_WGRAD_XCD=0: always the plain grid.
+// is more than one column tile to share operands; else the plain (tile, split) grid.
 static dim3 wgrad_grouped_grid(WGKMulti& m, int smax) {
-    static const int on = [] { const char* e = getenv("BMP_WGRAD_XCD"); return e ? atoi(e) : 1; }();
     const int T = m.ty0[BMP_WG_MAXP];
     m.smax = smax; m.grouped = 0;
     {   // problems with different part counts (row lists): exactly the work items, no holes in the grid -- a (tile, part) grid
@@ -1321,7 +1158,7 @@ static dim3 wgrad_grouped_grid(WGKMulti& m, int smax) {
             return dim3(total, 1, 1);
         }
     }
-    if (on && T > 1 && smax >= 8) {
+    if (T > 1 && smax >= 8) {
         const int G = smax >> 3;
         const int slots = G * T + ((smax - 8 * G) * T + 7) / 8;
         if (slots <= 64) { m.grouped = 1; return dim3(8 * slots, 1, 1); }
@@ -1579,7 +1416,7 @@ size_t bmp_wgrad_fused_ws_floats(const WGArgs* a, int n) {
     return tot;
 }
 
-bool bmp_wgrad_fused_lists_ok(int N) { return wgrad_dma_enabled() && N > 0 && (N % WD_RS) == 0; }
+bool bmp_wgrad_fused_lists_ok(int N) { return N > 0 && (N % WD_RS) == 0; }
 
 int bmp_launch_wgrad_fused(const WGArgs* a, int n, float* ws, hipStream_t st, int kid) {
     BMP_REQUIRE(n >= 1 && n <= BMP_WG_MAXP && ws != nullptr);

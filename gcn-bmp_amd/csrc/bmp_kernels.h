@@ -53,7 +53,7 @@ struct RGArgs {
 int bmp_launch_rowgemm(const RGArgs& a, int n_tiles, int epi, hipStream_t st);
 // generic epilogue, rows through a.ridx / a.rcnt; n_tiles_cap: tiles of the longest possible list (all rows)
 int bmp_launch_rowgemm_listed(const RGArgs& a, int n_tiles_cap, hipStream_t st);
-bool bmp_rowgemm_listed_ok(const RGArgs& a);      // the listed form exists for the LDS-staged kernel only (weight alignment; BMP_ROWGEMM_DIRECT unset)
+bool bmp_rowgemm_listed_ok(const RGArgs& a);      // the listed form exists for the LDS-staged kernel only (16-byte weight pieces)
 // n <= 3 independent problems (generic epilogue) in ONE launch
 int bmp_launch_rowgemm_multi(const RGArgs* a, const int* n_tiles, int n, hipStream_t st);
 
@@ -92,7 +92,7 @@ int bmp_launch_wgrad_multi(const WGArgs* a, int n, float* ws, hipStream_t st);
 // n <= BMP_WG_MAXP problems over the SAME rows (K <= 128; X2, column skips, zero-only problems and row lists allowed) as ONE
 // GEMM launch and ONE reduction launch: the weight gradients of a fused GGNN step / RelGCN layer.
 #define BMP_WG_MAXP 8
-bool bmp_wgrad_fused_lists_ok(int N);        // row lists need the LDS-DMA body (BMP_WGRAD_DMA != 0, N a multiple of 16)
+bool bmp_wgrad_fused_lists_ok(int N);        // row lists walk whole stages of the LDS-DMA body: N a multiple of 16
 size_t bmp_wgrad_fused_ws_floats(const WGArgs* a, int n);
 int bmp_launch_wgrad_fused(const WGArgs* a, int n, float* ws, hipStream_t st, int kid);
 

@@ -12,10 +12,8 @@
  *     enqueues kernels on `stream`.  What the library does remember, process-wide: (i) which
  *     (kernel, device) pairs already had hipFuncAttributeMaxDynamicSharedMemorySize raised
  *     (lock-free, per device: one process may drive several devices, from several host threads);
- *     (ii) A/B switches read once from the environment (BMP_WGRAD_DMA, BMP_WGRAD_XCD,
- *     BMP_STEP_WGRAD_UNFUSED, BMP_ROWGEMM_FORM / _DIRECT: diagnostics of tools/ and tests/,
- *     BMP_ROWGEMM_NO_THIN, BMP_ROWGEMM_SCALAR_EPI);
- *     (iii) the opt-in event timer bmp_prof_*.  None of them changes a result.  The code object
+ *     (ii) the opt-in event timer bmp_prof_*.  Neither changes a result, and the library reads no
+ *     environment variables.  The code object
  *     also holds one read-only device array of 128 zero floats (what a listed weight-gradient
  *     problem reads past the end of its list).
  *   - row-indexed arrays use the packed layout of bmp/packed.py: N = n_tiles * bmp_tile_rows()
@@ -125,7 +123,9 @@ int bmp_gru_state_bwd(const float* dsout, const float* hd, const float* m, const
  * wgrad reduces over the N rows: o1 [d x 7d] = h^T.gda (cols [0,4d): dWT as [k][e*d+c]; cols [4d,7d): dAT rows
  * 0..d-1), o2 [d x 3d] = m^T.da (dAT rows d..2d-1), dUcT [d x d], cs [7d] = column sums (dbE | db); all of it is ONE
  * GEMM launch + ONE fixed-order reduction.  first != 0 (the GRU's first call after reset has no r gate): the da_r columns
- * of gda are neither written by bwd nor read by wgrad and count as zeros. */
+ * of gda are neither written by bwd nor read by wgrad and count as zeros.
+ * wgrad needs N a multiple of 32 (of 8 at d = 32) and 16-byte aligned operands; otherwise it returns a non-zero code
+ * and writes nothing. */
 /* The forward launches take a tile range: tiles tile0 .. tile0 + n_tiles - 1 of the WHOLE arrays passed (a step is
  * tile-local: molecules never straddle tiles), so that two halves of a batch can run as two chains on two streams.
  * mt_row0 / mt_nblk (both NULL: tile t = rows [128 t, 128 t + 128)): the tile table of the encoder layout
@@ -176,7 +176,8 @@ int bmp_type_rows_live(const int* csr_ptr, const int* csr_col, const int* row_mo
  * are K4-packed as for bmp_ggnn_step_*.  fwd saves wdeg [N x 4] (weighted degree per bond type).
  * bwd writes dh [N x d] and gda [N x 5d] = [G_0..G_3 (transposed-gathered dpre per bond type) | dpre].
  * wgrad: o1 [d x 5d] = h^T.gda (cols [0,4d): dWT as [k][e*d+c]; cols [4d,5d): dWsT), dbE [4 x d] = wdeg^T.dpre,
- * cs [5d] = column sums of gda (cs[4d:] = dbs). */
+ * cs [5d] = column sums of gda (cs[4d:] = dbs).  wgrad needs N a multiple of 32 and 16-byte aligned operands; otherwise
+ * it returns a non-zero code and writes nothing. */
 int bmp_relgcn_layer_supported(int d_in, int d_out);
 int bmp_relgcn_layer_fwd(const float* h, int tile0, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
                          const float* WT, const float* bE, const float* WsT, const float* bs, int act, float* out,

@@ -132,6 +132,40 @@ def test_step_wgrad_over_the_live_rows_of_a_fixed_stride_batch(first):
         close(b_, a_.double(), f"{name} over the live rows vs all rows", tol=2e-5, floor=1e-3 * float(a_.abs().max()) + 1e-12)
 
 
+def test_step_and_layer_wgrad_reject_an_unaligned_gda():
+    """Handed row lists and a gda that is not 16-byte aligned (a one-float-offset view of a real allocation), the step's and the
+    layer's weight-gradient calls return an argument-check code and write nothing: there is no second path that would read the
+    G_e blocks a backward told to skip them (skip_zero_g) left unwritten.  The same calls on the aligned view succeed."""
+    from bmp import _lib
+    from bmp._lib import ptr, stream
+    L = _lib.lib()
+    pb = _batch(160, seed=5)
+    dev = pb.device
+    N, d = pb.n_rows, 128
+    assert L.bmp_step_wgrad_lists_used(N, d) == 1
+    idx, cnt = pb.type_rows_T()
+    h, m, rz, wdeg = torch.randn(N, d, device=dev), torch.randn(N, d, device=dev), torch.rand(N, 2 * d, device=dev), torch.rand(N, 4, device=dev)
+    gbuf = torch.randn(N * 7 * d + 4, device=dev) * 1e-2
+    full = lambda *s: torch.full(s, 7.0, device=dev)
+    sws = torch.empty(L.bmp_ggnn_step_wgrad_ws_floats(N, d), device=dev)
+    lws = torch.empty(L.bmp_relgcn_layer_wgrad_ws_floats(N, d), device=dev)
+    for off in (1, 0):
+        outs = [full(d, 7 * d), full(d, 3 * d), full(d, d), full(7 * d)]
+        gda = gbuf[off:off + N * 7 * d].view(N, 7 * d)
+        assert (gda.data_ptr() % 16 != 0) == (off == 1)
+        rc = L.bmp_ggnn_step_wgrad(ptr(h), ptr(m), ptr(rz), ptr(gda), N, d, 0, *(ptr(t) for t in outs), 0, ptr(idx), ptr(cnt), None,
+                                   None, ptr(sws), sws.numel(), stream())
+        assert (rc < -1000) if off else (rc == 0), (off, rc)
+        louts = [full(d, 5 * d), full(4, d), full(5 * d)]
+        gda = gbuf[off:off + N * 5 * d].view(N, 5 * d)
+        rc = L.bmp_relgcn_layer_wgrad(ptr(h), ptr(wdeg), ptr(gda), N, d, *(ptr(t) for t in louts), 0, ptr(idx), ptr(cnt), ptr(lws),
+                                      lws.numel(), stream())
+        assert (rc < -1000) if off else (rc == 0), (off, rc)
+        torch.cuda.synchronize()
+        for t in outs + louts:
+            assert bool((t == 7.0).all()) == (off == 1)
+
+
 def test_lists_off_switch_reaches_the_library():
     """BMP_WGRAD_LISTS=0 (bench.py's A/B): the planned step passes no lists and still equals the oracle (the all-rows launches are
     what rounds 1-3 tested); checked in a child process because the switch is read at import."""

@@ -1,5 +1,5 @@
 """Time the row GEMM (bmp_linear_fwd) alone on the shapes of config C4 (d = 256): usage
-   [BMP_ROWGEMM_FORM=1] python tools/rowgemm_probe.py"""
+   python tools/rowgemm_probe.py"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "gcn-bmp_amd")):
