@@ -16,6 +16,9 @@ import torch.distributed as dist
 from torch import nn
 from torch.autograd import Function
 
+from .optim_hooks import HOOK_TYPES, SUMSQ_PARTS_MAX, GradientClipping, Lasso, WeightDecay  # noqa: F401  (re-exported)
+from . import optim_hooks as _hooks
+
 
 class _Unflatten(Function):
     """flat parameter buffer -> the individual parameter tensors (views).  The backward writes all
@@ -60,7 +63,8 @@ class _Unflatten(Function):
 class FlatAdam:
     """Flattens a module's parameters and gradients into two contiguous buffers (the parameters
     become views) and applies chainer.optimizers.Adam (train_ddi_modify.py:289):
-    alpha_t = alpha*sqrt(1-b2^t)/(1-b1^t);  p -= alpha_t*m/(sqrt(v)+eps) + weight_decay_rate*p."""
+    alpha_t = alpha*sqrt(1-b2^t)/(1-b1^t);  p -= alpha_t*m/(sqrt(v)+eps) + weight_decay_rate*p.
+    Chainer's gradient hooks (GradientClipping, WeightDecay, Lasso: bmp.optim_hooks) go in with ``add_hook``."""
 
     def __init__(self, module: nn.Module, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay_rate=0.0,
                  process_group: Optional["dist.ProcessGroup"] = None):
@@ -94,6 +98,29 @@ class FlatAdam:
         self.plan = None
         self._plan_tried = False
         self._gscale = 1.0
+        self._hooks = {}                    # name -> hook, in the order added
+        self._partials = None               # bmp_grad_sumsq_partials' output, allocated with the first clip hook
+
+    def add_hook(self, hook, name: Optional[str] = None) -> None:
+        """chainer.Optimizer.add_hook for the hooks of bmp.optim_hooks: they run before the update rule in the order they
+        were added.  One hook of each kind; a name (default: the hook's ``name``) may be used once."""
+        if not isinstance(hook, HOOK_TYPES):
+            raise TypeError(f"FlatAdam runs GradientClipping, WeightDecay and Lasso hooks, not {type(hook).__name__}")
+        if any(type(h) is type(hook) for h in self._hooks.values()):
+            raise ValueError(f"a {type(hook).__name__} hook is already set")
+        name = hook.name if name is None else name
+        if name in self._hooks:
+            raise KeyError(f"hook {name} already exists")
+        if isinstance(hook, GradientClipping) and self.flat.is_cuda and self._partials is None:
+            self._partials = torch.empty(SUMSQ_PARTS_MAX, dtype=torch.float32, device=self.flat.device)
+        self._hooks[name] = hook
+
+    def remove_hook(self, name: str) -> None:
+        del self._hooks[name]
+
+    def hook_order(self) -> int:
+        """The kinds of the hooks set, in order (bmp.optim_hooks.hook_order); 0 without hooks."""
+        return _hooks.hook_order(self._hooks.values())
 
     def zero_grad(self) -> None:
         self.grad.zero_()
@@ -225,16 +252,40 @@ class FlatAdam:
             from . import _lib
             from ._lib import check, ptr, stream
             a_dev = getattr(self, "_alpha_dev", None)        # set by GraphedTrainStep: alpha_t lives on the device there
+            if self._hooks:
+                self._hooked_step(a_t, a_dev)
+                self._gscale = 1.0
+                return
             check(_lib.lib().bmp_adam_step(ptr(self.flat), ptr(g), ptr(self.m), ptr(self.v), self.flat.numel(), a_t,
                                            ptr(a_dev), self.beta1, self.beta2, self.eps, self.wd, self._gscale, stream()),
                   "bmp_adam_step")
             self._gscale = 1.0
             return
+        if self._hooks:
+            g = _hooks.apply_cpu(g, self.flat, self._hooks.values())
         self.m.mul_(self.beta1).add_(g, alpha=1.0 - self.beta1)
         self.v.mul_(self.beta2).addcmul_(g, g, value=1.0 - self.beta2)
         if self.wd:
             self.flat.mul_(1.0 - self.wd)
         self.flat.addcdiv_(self.m, self.v.sqrt().add_(self.eps), value=-a_t)
+
+    def _hooked_step(self, a_t, a_dev) -> None:
+        """The hooks and the update on the GPU: the clip's partial sums of squares (when a clip is set), then one launch of
+        hooks + Adam.  Their hyperparameters come from the hook objects, or from ``_hook_dev`` (GraphedTrainStep)."""
+        from . import _lib
+        from ._lib import check, ptr, stream
+        hooks = list(self._hooks.values())
+        order = _hooks.hook_order(hooks)
+        thr, l2, l1 = _hooks.hook_values(hooks)
+        h_dev = getattr(self, "_hook_dev", None)
+        parts = self._partials if any(h.code == _hooks.CLIP for h in hooks) else None
+        n, L, st = self.flat.numel(), _lib.lib(), stream()
+        if parts is not None:
+            check(L.bmp_grad_sumsq_partials(ptr(parts), ptr(self.grad), ptr(self.flat), n, self._gscale, l2, l1, ptr(h_dev),
+                                            order, st), "bmp_grad_sumsq_partials")
+        check(L.bmp_adam_step_hooked(ptr(self.flat), ptr(self.grad), ptr(self.m), ptr(self.v), n, a_t, ptr(a_dev), self.beta1,
+                                     self.beta2, self.eps, self.wd, self._gscale, thr, l2, l1, ptr(h_dev), order, ptr(parts),
+                                     None, st), "bmp_adam_step_hooked")
 
 
 def shard(n_items: int, rank: int, world: int):
@@ -263,10 +314,14 @@ class GraphedTrainStep:
         self.model, self.opt, self.warmup = model, opt, warmup
         self.graphs = {}
         self._alpha = torch.zeros(1, dtype=torch.float32, device=opt.flat.device)
+        self._hook_vals = torch.zeros(3, dtype=torch.float32, device=opt.flat.device)     # {threshold, l2, l1}
 
     def _set_alpha(self) -> None:
         o = self.opt
         self._alpha.fill_(o.alpha * math.sqrt(1.0 - o.beta2 ** (o.t + 1)) / (1.0 - o.beta1 ** (o.t + 1)))
+        if o._hooks:                        # the hooks' current thresholds / rates: changed between replays, they still apply
+            for k, val in enumerate(_hooks.hook_values(o._hooks.values())):
+                self._hook_vals[k].fill_(val)
 
     def _body(self, pb, t, static=None):
         plan = self.opt._layout_plan()
@@ -294,10 +349,12 @@ class GraphedTrainStep:
         o.collect_grads()
         o.all_reduce_grads()
         o._alpha_dev = self._alpha          # Adam reads alpha_t from the device in the recorded step (and only there: eager
-        try:                                # steps between replays take it from the host as ever)
+        o._hook_dev = self._hook_vals       # steps between replays take it from the host as ever); so do the hooks' values
+        try:
             o.step()
         finally:
             o._alpha_dev = None
+            o._hook_dev = None
         return loss
 
     def __call__(self, pb, t=None) -> torch.Tensor:
@@ -310,8 +367,8 @@ class GraphedTrainStep:
                 raise NotImplementedError("a step recorded on a fixed-shape batch is a single-rank path here: the RCCL all-reduce "
                                           "inside a HIP graph is untested; use the packed layouts for N > 1")
             pb, t = static.pb, static.t
-        key = (id(pb), id(t))
         o = self.opt
+        key = (id(pb), id(t), o.hook_order())      # a hook added or removed after recording: a new recording
         if key not in self.graphs:
             # warm-up on a side stream (allocator, lazy builds), with the optimizer state put back afterwards
             saved = (o.flat.clone(), o.m.clone(), o.v.clone(), o.t)

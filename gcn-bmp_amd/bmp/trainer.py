@@ -12,7 +12,8 @@ hot path with chainer.training (train_binary.py:530-665, train_ddi_modify.py:280
   resident in HBM: every batch collated on the device, in the per-instance layout or in the encoder layout (optionally with
   every distinct molecule of the batch encoded once), this rank's share of each global batch;
 * ``fit``: StandardUpdater + the extensions above as one loop over packed batches, log entries named as the
-  reference's PrintReport columns (train_binary.py:650-658).
+  reference's PrintReport columns (train_binary.py:650-658).  The reference's optimizer hooks (GradientClipping, WeightDecay,
+  Lasso: train_binary.py:538-543) belong to the optimizer: ``opt.add_hook(...)`` on the FlatAdam handed to ``fit``.
 
 Metrics are plain numpy (no sklearn at run time); tests/test_trainer.py checks them against sklearn.
 """

@@ -405,6 +405,28 @@ int bmp_gather_sum(float* dst, int n, const float* src, const int* idx, int K, i
 int bmp_adam_step(float* p, const float* g, float* m, float* v, int n, float alpha_t, const float* alpha_t_dev, float beta1,
                   float beta2, float eps, float weight_decay_rate, float grad_scale, bmp_stream_t stream);
 
+/* ---- Chainer's optimizer hooks in front of Adam (train_binary.py:538-543: optimizer.add_hook of GradientClipping(max_norm),
+ * WeightDecay(l2_rate), Lasso(l1_rate), in that order).  Hooks run in the order they were added, each on the gradient as the
+ * hooks before it left it, starting from g * grad_scale:
+ *   clip:  g *= min(1, threshold / sqrt(sum g^2)) in fp32 (a zero norm gives 1);
+ *   decay: g += l2_rate * p;   Lasso: g += l1_rate * sign(p), sign(0) = 0   (p before this step's update);
+ * then bmp_adam_step's rule, Adam's own weight_decay_rate included.
+ * hook_order: the hooks as 2-bit codes, first hook in bits 0-1, then 2-3, 4-5; 1 = clip, 2 = decay, 3 = Lasso, 0 ends the list;
+ * each kind at most once.  hook_dev (device, 3 floats {threshold, l2_rate, l1_rate}, may be NULL) overrides the three
+ * scalars, as alpha_t_dev does alpha_t.
+ * bmp_grad_sumsq_partials (needs a clip in hook_order): partials[P] (P = ceil(n / 2048) capped at 256, a function of n
+ * alone; allocate 256) = the sums of squares of fixed slices of the gradient the clip sees.  g and p need only 4-byte
+ * alignment; p may be NULL when the clip comes first.
+ * bmp_adam_step_hooked: the hooks and the update in one launch; with a clip, every block reduces the same partials in the
+ * same order (a bit-identical scale everywhere) and norm_out (device, 1 float, may be NULL) receives the global norm.
+ * partials and norm_out must be NULL without a clip. */
+int bmp_grad_sumsq_partials(float* partials, const float* g, const float* p, int n, float grad_scale, float l2_rate,
+                            float l1_rate, const float* hook_dev, int hook_order, bmp_stream_t stream);
+int bmp_adam_step_hooked(float* p, const float* g, float* m, float* v, int n, float alpha_t, const float* alpha_t_dev,
+                         float beta1, float beta2, float eps, float weight_decay_rate, float grad_scale, float clip_threshold,
+                         float l2_rate, float l1_rate, const float* hook_dev, int hook_order, const float* partials,
+                         float* norm_out, bmp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
