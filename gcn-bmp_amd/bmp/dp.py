@@ -9,6 +9,7 @@ bucketing or overlap).
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from typing import Optional
 
 import torch
@@ -64,10 +65,17 @@ class FlatAdam:
     """Flattens a module's parameters and gradients into two contiguous buffers (the parameters
     become views) and applies chainer.optimizers.Adam (train_ddi_modify.py:289):
     alpha_t = alpha*sqrt(1-b2^t)/(1-b1^t);  p -= alpha_t*m/(sqrt(v)+eps) + weight_decay_rate*p.
-    Chainer's gradient hooks (GradientClipping, WeightDecay, Lasso: bmp.optim_hooks) go in with ``add_hook``."""
+    Chainer's gradient hooks (GradientClipping, WeightDecay, Lasso: bmp.optim_hooks) go in with ``add_hook``.
+
+    ``grad_reduce`` says what the update sees of the ranks' gradients (each the gradient of that rank's mean loss):
+    ``"mean"`` (the default) their mean; ``"sum"`` their sum, which is what Chainer's ``ParallelUpdater`` hands to the
+    optimizer (``model_main.addgrads(other)``, then ``optimizer.update()``; recalled third-party behaviour, SURVEY.md
+    Appendix B).  Adam barely tells the two apart, but the hooks' clip threshold and decay rates act on the one chosen."""
 
     def __init__(self, module: nn.Module, alpha=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay_rate=0.0,
-                 process_group: Optional["dist.ProcessGroup"] = None):
+                 process_group: Optional["dist.ProcessGroup"] = None, grad_reduce: str = "mean"):
+        if grad_reduce not in ("mean", "sum"):
+            raise ValueError(f"grad_reduce {grad_reduce!r}: 'mean' or 'sum'")
         params = [p for p in module.parameters() if p.requires_grad]
         if not params:
             raise ValueError("module has no parameters")
@@ -94,6 +102,7 @@ class FlatAdam:
         self.t = 0
         self.alpha, self.beta1, self.beta2, self.eps, self.wd = alpha, beta1, beta2, eps, weight_decay_rate
         self.group = process_group
+        self.grad_reduce = grad_reduce
         self.world = dist.get_world_size(process_group) if dist.is_available() and dist.is_initialized() else 1
         self.plan = None
         self._plan_tried = False
@@ -234,15 +243,23 @@ class FlatAdam:
         if self.world > 1:
             dist.broadcast(self.flat, src=src, group=self.group)
 
+    def reduce_scale(self) -> float:
+        """The factor the update applies to the all-reduced gradient: 1/W for ``grad_reduce="mean"``, 1 for ``"sum"`` and at
+        W = 1."""
+        return 1.0 / self.world if self.world > 1 and self.grad_reduce == "mean" else 1.0
+
     def all_reduce_grads(self) -> None:
         """The step's single collective: sum over ranks, then the mean (each rank's loss is the
-        mean over its own shard)."""
+        mean over its own shard) -- or the sum as it is, with ``grad_reduce="sum"``."""
         if self.world > 1:
             dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.group)
+            scale = self.reduce_scale()
+            if scale == 1.0:
+                return
             if self.grad.is_cuda:
-                self._gscale = 1.0 / self.world      # folded into the Adam kernel
+                self._gscale = scale                 # folded into the Adam kernel
             else:
-                self.grad.mul_(1.0 / self.world)
+                self.grad.mul_(scale)
 
     def step(self) -> None:
         self.t += 1
@@ -306,6 +323,15 @@ class GraphedTrainStep:
     resident already), the flat parameter / moment buffers, and Adam's step-dependent factor alpha_t, which is read
     from a one-element device tensor updated before every replay.  Host-side decisions made while recording (which
     gradient buffer a kernel overwrites, which it accumulates into) are the same for every replay of one batch.
+
+    With more than one rank (``opt.world > 1``) a step is recorded as TWO graphs per batch: A = the static batch's
+    ``reset_derived`` + ``emit`` (static form), forward, loss, backward and ``collect_grads``; B = the update (the clip's
+    partial sums and ``bmp_adam_step_hooked`` with hooks set, ``bmp_adam_step`` without), with the gradient scale of
+    ``opt.grad_reduce`` (1/W or 1) fixed in it.  A call replays A, runs ``opt.all_reduce_grads()`` eagerly on the current
+    stream -- on the flat gradient A writes and B reads --, then replays B.  The collective stays outside the graphs because
+    that is the form both backends run: gloo cannot run inside a recording, and an RCCL all-reduce recorded into a graph has
+    never run on this stack.  No collective is issued while a recording is open; the warm-up before recording runs whole
+    eager steps, collective included, the same number on every rank.  The replay speed over RCCL is unmeasured.
     """
 
     def __init__(self, model, opt: "FlatAdam", warmup: int = 2):
@@ -323,18 +349,28 @@ class GraphedTrainStep:
             for k, val in enumerate(_hooks.hook_values(o._hooks.values())):
                 self._hook_vals[k].fill_(val)
 
-    def _body(self, pb, t, static=None):
+    @contextmanager
+    def _in_line(self):
         plan = self.opt._layout_plan()
         if plan is None:
-            return self._body_streams(pb, t, static)
+            yield
+            return
         was = getattr(plan, "in_line", False)
         plan.in_line = True                 # one in-order chain: what a replay runs back to back (bmp/plan.py: prepare)
         try:
-            return self._body_streams(pb, t, static)
+            yield
         finally:
             plan.in_line = was
 
-    def _body_streams(self, pb, t, static=None):
+    def _body(self, pb, t, static=None):
+        with self._in_line():
+            loss = self._grads(pb, t, static)
+            self.opt.all_reduce_grads()
+            self._update()
+            return loss
+
+    def _grads(self, pb, t, static=None):
+        """Forward, loss, backward, collect_grads: the step up to the flat gradient (graph A at world > 1)."""
         o = self.opt
         if static is not None:
             # a batch at fixed addresses (bmp.packed.StaticPairBatch): its arrays are written by the first launch of the step,
@@ -347,7 +383,11 @@ class GraphedTrainStep:
             loss = self.model.loss(o.functional_forward(pb), t)
         loss.backward()
         o.collect_grads()
-        o.all_reduce_grads()
+        return loss
+
+    def _update(self) -> None:
+        """The hooks and Adam (graph B at world > 1)."""
+        o = self.opt
         o._alpha_dev = self._alpha          # Adam reads alpha_t from the device in the recorded step (and only there: eager
         o._hook_dev = self._hook_vals       # steps between replays take it from the host as ever); so do the hooks' values
         try:
@@ -355,22 +395,18 @@ class GraphedTrainStep:
         finally:
             o._alpha_dev = None
             o._hook_dev = None
-        return loss
 
     def __call__(self, pb, t=None) -> torch.Tensor:
         """One step on the batch ``(pb, t)`` -- or on a ``StaticPairBatch`` (``t`` is then its own label array): ONE graph
-        serves every batch loaded into it."""
+        (one pair of graphs at world > 1) serves every batch loaded into it."""
         static = pb if callable(getattr(pb, "emit", None)) else None
         if static is not None:
-            if self.opt.world > 1:
-                # (one rank per GPU records its own step; the all-reduce inside a recording has never run on this stack)
-                raise NotImplementedError("a step recorded on a fixed-shape batch is a single-rank path here: the RCCL all-reduce "
-                                          "inside a HIP graph is untested; use the packed layouts for N > 1")
             pb, t = static.pb, static.t
         o = self.opt
         key = (id(pb), id(t), o.hook_order())      # a hook added or removed after recording: a new recording
         if key not in self.graphs:
-            # warm-up on a side stream (allocator, lazy builds), with the optimizer state put back afterwards
+            # warm-up on a side stream (allocator, lazy builds), with the optimizer state put back afterwards; at world > 1
+            # these are whole eager steps, all-reduce included, the same number on every rank
             saved = (o.flat.clone(), o.m.clone(), o.v.clone(), o.t)
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -380,14 +416,41 @@ class GraphedTrainStep:
                     self._body(pb, t, static)
             torch.cuda.current_stream().wait_stream(s)
             o.flat.copy_(saved[0]); o.m.copy_(saved[1]); o.v.copy_(saved[2]); o.t = saved[3]
+            self.graphs[key] = self._record(pb, t, static)
+        rec = self.graphs[key]
+        self._set_alpha()
+        if o.world == 1:
+            g, loss, _pb, _t = rec
+            g.replay()
+        else:
+            ga, gb, loss, grad, _pb, _t = rec
+            ga.replay()
+            o.grad = grad                       # the flat gradient A writes and B reads (an eager step may have rebound it)
+            o.all_reduce_grads()
+            o._gscale = 1.0                     # (B holds the scale it was recorded with)
+            gb.replay()
+        o.t += 1
+        return loss
+
+    def _record(self, pb, t, static):
+        o = self.opt
+        t_before = o.t
+        if o.world == 1:
             g = torch.cuda.CUDAGraph()
-            t_before = o.t
             with torch.cuda.graph(g):
                 loss = self._body(pb, t, static)
             o.t = t_before                      # recording does not execute: the step count advances on replay
-            self.graphs[key] = (g, loss, pb, t)
-        g, loss, _pb, _t = self.graphs[key]
-        self._set_alpha()
-        g.replay()
-        o.t += 1
-        return loss
+            return g, loss, pb, t
+        ga, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+        with self._in_line():
+            with torch.cuda.graph(ga):
+                loss = self._grads(pb, t, static)
+            grad = o.grad
+            o._gscale = o.reduce_scale()        # the all-reduce's scale, a launch argument of B's update kernel
+            try:
+                with torch.cuda.graph(gb):
+                    self._update()
+            finally:
+                o._gscale = 1.0
+        o.t = t_before
+        return ga, gb, loss, grad, pb, t

@@ -173,21 +173,30 @@ class PairBatches:
     loaded into ONE fixed-shape batch (bmp.packed.StaticPairBatch: the same object is yielded every time, its contents change),
     on which ``fit`` replays one recorded HIP graph per step -- the way to run small batches such as the reference's default of
     32 pairs (train_ddi_modify.py:196), where a step is ~55 launches of one workgroup round each; the short remainder of a pass
-    comes as a usual packed batch.  With ``world`` > 1 a global
-    batch is ``batch_size * world`` pairs and this rank takes its contiguous share (a remainder smaller than ``world`` is
-    left out, so that no rank steps on an empty batch)."""
+    comes as a usual packed batch.
+
+    With ``world`` > 1 a global batch is ``batch_size * world`` pairs and this rank takes its share of it (a remainder smaller
+    than ``world`` is left out, so that no rank steps on an empty batch): ``share`` "contiguous" is the slice
+    [r * batch_size, (r + 1) * batch_size); "strided" is ``sel[r::world]``, the share Chainer's ``ParallelUpdater`` gives
+    device r (recalled third-party behaviour).  Every full global batch gives each rank exactly
+    ``batch_size`` pairs either way, so "static" serves any ``world``: ``fit`` then replays the step recorded as two graphs
+    with the gradient all-reduce between them (bmp.dp.GraphedTrainStep).  The reference's ``--multi-gpu=True --batchsize 32``
+    is ``batch_size=16, world=2, share="strided"`` with ``FlatAdam(..., grad_reduce="sum")`` (INTEGRATION.md)."""
 
     def __init__(self, dstore, idx1: np.ndarray, idx2: np.ndarray, labels: np.ndarray, batch_size: int, shuffle: bool = False,
-                 seed: int = 0, layout: str = "instance", dedup: bool = False, rank: int = 0, world: int = 1):
+                 seed: int = 0, layout: str = "instance", dedup: bool = False, rank: int = 0, world: int = 1,
+                 share: str = "contiguous"):
         if layout not in ("instance", "encoder", "static"):
             raise ValueError(f"layout {layout!r}: 'instance', 'encoder' or 'static'")
+        if share not in ("contiguous", "strided"):
+            raise ValueError(f"share {share!r}: 'contiguous' or 'strided'")
         if dedup and layout != "encoder":
             raise ValueError("dedup needs layout='encoder'")
         if not (len(idx1) == len(idx2) == len(labels)):
             raise ValueError("idx1, idx2 and labels must have one entry per pair")
         self.dstore, self.i1, self.i2, self.lab = dstore, np.asarray(idx1), np.asarray(idx2), np.asarray(labels)
         self.B, self.shuffle, self.seed, self.layout, self.dedup = int(batch_size), shuffle, seed, layout, dedup
-        self.rank, self.world, self.epoch = rank, world, 0
+        self.rank, self.world, self.share, self.epoch = rank, world, share, 0
 
     def __len__(self) -> int:
         g = self.B * self.world
@@ -203,6 +212,9 @@ class PairBatches:
             sel = order[lo:lo + g]
             if len(sel) < self.world:
                 break
+            if self.share == "strided":
+                yield sel[self.rank::self.world]
+                continue
             q, r = divmod(len(sel), self.world)          # ranks 0..r-1 take one pair more: no rank is left without pairs
             a = self.rank * q + min(self.rank, r)
             yield sel[a:a + q + (1 if self.rank < r else 0)]
