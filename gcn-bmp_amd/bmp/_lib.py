@@ -53,6 +53,22 @@ SIGNATURES = {
     "bmp_relgcn_layer_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "bmp_relgcn_layer_wgrad_ws_floats": (_Z, [_I, _I]),
     "bmp_relgcn_layer_wgrad": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    "bmp_nfp_rows": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P]),
+    "bmp_nfp_deg_rows_ws_ints": (_Z, [_I]),
+    "bmp_nfp_deg_rows": (_I, [_P, _I, _P, _P, _P, _P]),
+    "bmp_nfp_layer_fwd": (_I, [_P, _I, _I, _I] + [_P] * 10),
+    "bmp_nfp_layer_bwd": (_I, [_P, _P, _I, _I, _I] + [_P] * 11),
+    "bmp_nfp_layer_wgrad_ws_floats": (_Z, [_I, _I, _I]),
+    "bmp_nfp_layer_wgrad": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _Z, _P]),
+    "bmp_nfp_readout_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _P]),
+    "bmp_nfp_readout_bwd_ws_floats": (_Z, [_I, _I, _I]),
+    "bmp_nfp_readout_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "bmp_nfp_layer_supported": (_I, [_I]),
+    "bmp_nfp_layer_tile_fwd": (_I, [_P, _I, _I] + [_P] * 10),
+    "bmp_nfp_layer_tile_bwd": (_I, [_P, _P, _I, _I] + [_P] * 10),
+    "bmp_nfp_readout_tile_supported": (_I, [_I, _I]),
+    "bmp_nfp_readout_tile_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "bmp_nfp_readout_tile_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bmp_readout_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "bmp_readout_bwd_ws_floats": (_Z, [_I, _I, _I, _I]),
     "bmp_readout_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _P, _P]),

@@ -929,3 +929,140 @@ class PRelLayerFn(Function):
         dx = _rel_bwd(dout.contiguous(), out, x, wdeg, ctx.pb, W["Wnat_p"], W["Ws_p"], ctx.act, G["o1"], G["dbE"], G["cs"],
                       0 if first else 1, ctx.state)
         return dx, None, None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Neural-fingerprint encoder (models/models/nfp.py; csrc/bmp_nfp.hip).  ``nd`` is the batch's derived NFP data
+# (bmp.nfp.nfp_derived): self_w, deg_class, deg_rows, deg_cnt.
+# ---------------------------------------------------------------------------------------------------------
+NFP_PATHS = {"layer_tile": 0, "layer_rows": 0, "readout_tile": 0, "readout_rows": 0}      # forward calls per kernel form
+
+
+def nfp_tile_ok(pb) -> bool:
+    """The fused NFP kernels take whole 128-row tiles whose molecules never straddle a tile."""
+    return pb.mt_row0 is None and not pb.oversized and pb.row_mol is not None
+
+
+class NFPLayerFn(Function):
+    """NFPUpdate.__call__ (nfp.py:36-62): out = sigmoid(fv . W_deg + B), fv = adj . h.  WT [7 x d_in x d_out] (K-major per
+    degree class), B [d_out] = the sum of the seven biases.  ``fused``: the per-tile MFMA kernels and the listed MFMA weight
+    gradient where the shape allows (d_in == d_out in {64, 128}, whole tiles); False: the row-wise kernels at every width."""
+
+    @staticmethod
+    def forward(ctx, x, WT, B, pb, nd, fused):
+        L = _lib.lib()
+        require_rows(x, "nfp layer: x")
+        _check_pb(pb, x)
+        N, d_in = x.shape
+        if WT.dim() != 3 or WT.shape[0] != 7 or WT.shape[1] != d_in or B.shape[0] != WT.shape[2]:
+            raise ValueError("nfp layer: weight shapes do not match x")
+        d_out = WT.shape[2]
+        WT = WT.contiguous(); B = B.contiguous()
+        fv = torch.empty(N, d_in, dtype=torch.float32, device=x.device)
+        out = torch.empty(N, d_out, dtype=torch.float32, device=x.device)
+        tile = bool(fused) and nfp_tile_ok(pb) and d_in == d_out and bool(L.bmp_nfp_layer_supported(d_in))
+        if tile:
+            WTp = torch.stack([pack_k4(WT[k]) for k in range(7)])
+            check(L.bmp_nfp_layer_tile_fwd(ptr(x), pb.n_tiles, d_in, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                                           ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(WTp), ptr(B), ptr(fv), ptr(out), stream()),
+                  "bmp_nfp_layer_tile_fwd")
+        else:
+            check(L.bmp_nfp_layer_fwd(ptr(x), pb.n_tiles, d_in, d_out, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                                      ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(WT), ptr(B), ptr(fv), ptr(out), stream()),
+                  "bmp_nfp_layer_fwd")
+        ctx.save_for_backward(WT, fv, out)
+        ctx.pb, ctx.nd, ctx.listed, ctx.tile = pb, nd, int(bool(fused)), tile
+        NFP_PATHS["layer_tile" if tile else "layer_rows"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        WT, fv, out = ctx.saved_tensors
+        pb, nd = ctx.pb, ctx.nd
+        dout = dout.contiguous()
+        N, d_in = fv.shape
+        d_out = out.shape[1]
+        dev = fv.device
+        Wnat = WT.transpose(1, 2).contiguous()
+        f = lambda *s_: torch.empty(*s_, dtype=torch.float32, device=dev)
+        dpre, dh = f(N, d_out), f(N, d_in)
+        if ctx.tile:
+            Wnp = torch.stack([pack_k4(Wnat[k]) for k in range(7)])
+            check(L.bmp_nfp_layer_tile_bwd(ptr(dout), ptr(out), pb.n_tiles, d_in, ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val),
+                                           ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(pb.row_w), ptr(Wnp), ptr(dpre), ptr(dh),
+                                           stream()), "bmp_nfp_layer_tile_bwd")
+        else:
+            dfv = f(N, d_in)
+            check(L.bmp_nfp_layer_bwd(ptr(dout), ptr(out), pb.n_tiles, d_in, d_out, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
+                                      ptr(pb.csrT_val), ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(pb.row_w), ptr(Wnat), ptr(dpre),
+                                      ptr(dfv), ptr(dh), stream()), "bmp_nfp_layer_bwd")
+        dWT, dB = f(7, d_in, d_out), f(d_out)
+        nws = L.bmp_nfp_layer_wgrad_ws_floats(N, d_in, d_out)
+        ws = _ws(nws, dev)
+        check(L.bmp_nfp_layer_wgrad(ptr(fv), ptr(dpre), N, d_in, d_out, ptr(nd["deg_rows"]), ptr(nd["deg_cnt"]), ptr(dWT), ptr(dB),
+                                    ctx.listed, ptr(ws), nws, stream()), "bmp_nfp_layer_wgrad")
+        return dh, dWT, dB, None, None, None
+
+
+class NFPReadoutFn(Function):
+    """NFPReadout.__call__ (nfp.py:83-91) added to the readouts of the layers before it (:163-166): returns
+    g_prev + sum over the molecule's positions of softmax_channels(h . WT + b), written in place into ``g_prev`` (None: a new
+    array).  WT [d x o], b [o]."""
+
+    @staticmethod
+    def forward(ctx, h, WT, b, pb, g_prev, fused=True):
+        L = _lib.lib()
+        require_rows(h, "nfp readout: h")
+        _check_pb(pb, h)
+        N, d = h.shape
+        if WT.dim() != 2 or WT.shape[0] != d or b.shape[0] != WT.shape[1]:
+            raise ValueError("nfp readout: weight shape does not match h")
+        o = WT.shape[1]
+        WT = WT.contiguous(); b = b.contiguous()
+        s = torch.empty(N, o, dtype=torch.float32, device=h.device)
+        if g_prev is None:
+            g = torch.empty(pb.n_mols, o, dtype=torch.float32, device=h.device)
+        else:
+            if tuple(g_prev.shape) != (pb.n_mols, o) or not g_prev.is_contiguous():
+                raise ValueError("nfp readout: g_prev must be a contiguous (n_mols, o) array")
+            g = g_prev
+            ctx.mark_dirty(g_prev)
+        tile = bool(fused) and nfp_tile_ok(pb) and bool(L.bmp_nfp_readout_tile_supported(d, o))
+        acc = 0 if g_prev is None else 1
+        if tile:
+            check(L.bmp_nfp_readout_tile_fwd(ptr(h), pb.n_tiles, d, o, ptr(pack_k4(WT)), ptr(b), ptr(pb.row_w), ptr(pb.row_mol),
+                                             ptr(s), ptr(g), acc, stream()), "bmp_nfp_readout_tile_fwd")
+        else:
+            check(L.bmp_nfp_readout_fwd(ptr(h), pb.n_tiles, d, o, ptr(WT), ptr(b), ptr(pb.row_w), ptr(pb.mol_row0), ptr(pb.mol_nrows),
+                                        pb.n_mols, ptr(s), ptr(g), acc, stream()), "bmp_nfp_readout_fwd")
+        ctx.save_for_backward(h, WT, s)
+        ctx.pb, ctx.has_prev, ctx.tile = pb, g_prev is not None, tile
+        NFP_PATHS["readout_tile" if tile else "readout_rows"] += 1
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        L = _lib.lib()
+        h, WT, s = ctx.saved_tensors
+        pb = ctx.pb
+        if pb.row_mol is None:
+            raise ValueError("nfp readout: the batch carries no row -> molecule map")
+        dg = dg.contiguous()
+        N, d = h.shape
+        o = WT.shape[1]
+        dev = h.device
+        Wnat = WT.t().contiguous()
+        dh = torch.empty_like(h)
+        dWT = torch.empty_like(WT)
+        db = torch.empty(o, dtype=torch.float32, device=dev)
+        nws = L.bmp_nfp_readout_bwd_ws_floats(N, d, o)
+        ws = _ws(nws, dev)
+        if ctx.tile:
+            check(L.bmp_nfp_readout_tile_bwd(ptr(dg), ptr(h), ptr(s), pb.n_tiles, d, o, ptr(pack_k4(Wnat)), ptr(pb.row_w),
+                                             ptr(pb.row_mol), ptr(dh), ptr(dWT), ptr(db), ptr(ws), nws, stream()),
+                  "bmp_nfp_readout_tile_bwd")
+        else:
+            check(L.bmp_nfp_readout_bwd(ptr(dg), ptr(h), ptr(s), pb.n_tiles, d, o, ptr(Wnat), ptr(pb.row_w), ptr(pb.row_mol), ptr(dh),
+                                        ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_nfp_readout_bwd")
+        return dh, dWT, db, None, (dg if ctx.has_prev else None), None

@@ -151,6 +151,10 @@ class PackedMolBatch:
     # 0: the tile table covers dense rows (tile t + 1 follows tile t).  R: tile t starts at row R t whatever its height (the
     # fixed-shape batch below); the fused step kernels then clear the rows of a tile's dead blocks in what they write.
     tile_stride: int = 0
+    # A batch packed from the dense NFP call form (bmp.nfp.pack_nfp_dense) carries the diagonal of its adjacency and the
+    # degree class of its rows, taken from the array as given: data of the batch, not derivable from the CSR.
+    nfp_self_w: Optional[torch.Tensor] = None      # (N,) float32
+    nfp_deg_class: Optional[torch.Tensor] = None   # (N,) int32 in 0..7
     _cache: dict = field(default_factory=dict, repr=False)
 
     def __post_init__(self):

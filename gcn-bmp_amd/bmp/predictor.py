@@ -145,6 +145,9 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
     elif encoder == "relgcn":
         from .relgcn import RelGCN
         enc = RelGCN(out_channels=out_dim, ch_list=[hidden_dim] * (n_layers + 1), scale_adj=True)
+    elif encoder == "nfp":                                                       # train_binary.py:274-276
+        from .nfp import NFP
+        enc = NFP(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers)
     else:
         raise ValueError('[ERROR] Invalid graph embedding encoder.')
     a = None

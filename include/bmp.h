@@ -190,6 +190,61 @@ int bmp_relgcn_layer_wgrad(const float* h, const float* wdeg, const float* gda, 
                            float* cs, int accumulate, const int* type_rows, const int* type_cnt, float* ws, size_t ws_floats,
                            bmp_stream_t stream);          /* type_rows / type_cnt: as bmp_ggnn_step_wgrad */
 
+/* ---- Neural-fingerprint encoder -- models/models/nfp.py (csrc/bmp_nfp.hip) ----
+ * ONE adjacency: every bond counts once whatever its type (csr_col >> 2 is the source row), plus a self loop of weight
+ * self_w [N] on the rows that have one (1 on real atoms, 0 on pad and dead rows).  deg_class [N] in 0..7: k when the COLUMN
+ * sum of the adjacency (self_w + the row's transposed-CSR values, nfp.py:157) equals k exactly, else 0.
+ * bmp_nfp_rows: self_w and deg_class of a batch packed from the store (a molecule's last row is its pad row).
+ * bmp_nfp_deg_rows: idx [7 x N], idx[(k - 1) * N + p] = the p-th row (ascending) of class k, cnt [7]; fixed order, no atomics;
+ * ws: bmp_nfp_deg_rows_ws_ints(N) ints.
+ * Layer (NFPUpdate.__call__ :36-62): fv = adj . h over the forward CSR; out = sigmoid(fv . W_deg + B), class 0: sigmoid(B).
+ * WT [7][d_in][d_out] (K-major per class), Wnat [7][d_out][d_in] (reference layout), B [d_out] = the sum of the seven biases.
+ * fwd saves fv [N x d_in].  bwd writes dpre [N x d_out] (0 on rows of weight 0) and dh [N x d_in]; dfv [N x d_in] is scratch.
+ * wgrad: dWT [7][d_in][d_out] over the class row lists, dB [d_out] = column sums of dpre over all rows; listed != 0 takes the
+ * MFMA launch over the row lists where the shape allows (64 <= d_in <= 128, d_out >= 64), 0 the row-wise kernel.
+ * Readout (NFPReadout.__call__ :83-91): g[mol] (=|+=) sum_rows row_w * softmax_channels(h . WT + b); WT [d x o], Wnat [o x d];
+ * saves s [N x o] (the softmax).  bwd: dh [N x d], dWT [d x o], db [o].  Channel counts are multiples of 4. */
+int bmp_nfp_rows(const int* csrT_ptr, const float* csrT_val, const int* row_mol, const int* mol_row0, const int* mol_nrows, int N,
+                 float* self_w, int* deg_class, bmp_stream_t stream);
+size_t bmp_nfp_deg_rows_ws_ints(int N);
+int bmp_nfp_deg_rows(const int* deg_class, int N, int* idx, int* cnt, int* ws, bmp_stream_t stream);
+int bmp_nfp_layer_fwd(const float* h, int n_tiles, int d_in, int d_out, const int* csr_ptr, const int* csr_col,
+                      const float* csr_val, const float* self_w, const int* deg_class, const float* WT, const float* B, float* fv,
+                      float* out, bmp_stream_t stream);
+int bmp_nfp_layer_bwd(const float* dout, const float* out, int n_tiles, int d_in, int d_out, const int* csrT_ptr,
+                      const int* csrT_col, const float* csrT_val, const float* self_w, const int* deg_class, const float* row_w,
+                      const float* Wnat, float* dpre, float* dfv, float* dh, bmp_stream_t stream);
+size_t bmp_nfp_layer_wgrad_ws_floats(int N, int d_in, int d_out);
+int bmp_nfp_layer_wgrad(const float* fv, const float* dpre, int N, int d_in, int d_out, const int* deg_rows, const int* deg_cnt,
+                        float* dWT, float* dB, int listed, float* ws, size_t ws_floats, bmp_stream_t stream);
+int bmp_nfp_readout_fwd(const float* h, int n_tiles, int d, int o, const float* WT, const float* b, const float* row_w,
+                        const int* mol_row0, const int* mol_nrows, int n_mols, float* s, float* g, int accumulate,
+                        bmp_stream_t stream);
+size_t bmp_nfp_readout_bwd_ws_floats(int N, int d, int o);
+int bmp_nfp_readout_bwd(const float* dg, const float* h, const float* s, int n_tiles, int d, int o, const float* Wnat,
+                        const float* row_w, const int* row_mol, float* dh, float* dWT, float* db, float* ws, size_t ws_floats,
+                        bmp_stream_t stream);
+
+/* The fused per-tile forms (exact-f32 MFMA; one workgroup per 128-row tile): d_in == d_out == d with bmp_nfp_layer_supported
+ * (64 or 128); readout with bmp_nfp_readout_tile_supported (d in {64, 128}, o a multiple of 8 up to 128).  The tile's rows are
+ * ranked by degree class and every 32-row block of the ranked tile is multiplied with the matrices of the classes it holds (rows of
+ * other classes zeroed in the A operand): work in proportion to the (block, class) pairs present, deterministic.  WTp / Wnp
+ * [7][d x d]: per class W^T (K-major) / W (reference layout) K4-packed as for bmp_ggnn_step_*; WoTp = W_o^T [d x o], the
+ * readout's Wnp = W_o [o x d], K4-packed.  Whole 128-row tiles only (no tile table).  Outputs and ws as the row-wise forms. */
+int bmp_nfp_layer_supported(int d);
+int bmp_nfp_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                           const float* self_w, const int* deg_class, const float* WTp, const float* B, float* fv, float* out,
+                           bmp_stream_t stream);
+int bmp_nfp_layer_tile_bwd(const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
+                           const float* csrT_val, const float* self_w, const int* deg_class, const float* row_w, const float* Wnp,
+                           float* dpre, float* dh, bmp_stream_t stream);
+int bmp_nfp_readout_tile_supported(int d, int o);
+int bmp_nfp_readout_tile_fwd(const float* h, int n_tiles, int d, int o, const float* WoTp, const float* b, const float* row_w,
+                             const int* row_mol, float* s, float* g, int accumulate, bmp_stream_t stream);
+int bmp_nfp_readout_tile_bwd(const float* dg, const float* h, const float* s, int n_tiles, int d, int o, const float* Wnp,
+                             const float* row_w, const int* row_mol, float* dh, float* dWT, float* db, float* ws, size_t ws_floats,
+                             bmp_stream_t stream);
+
 /* Gated-sum readout -- GGNN.readout models/ggnn.py:333-341 and GGNNReadout.__call__
  * models/readout/ggnn_readout.py:42-57.  g[mol] = sum_rows w * sigmoid(i(.)) * act_j(j(.)).
  * WT [(d+d0) x 2o] cols [i|j]; h0 may be NULL (d0 ignored).  Saves ij [N x 2o]. */
