@@ -72,6 +72,9 @@ SIGNATURES = {
     "bmp_readout_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "bmp_readout_bwd_ws_floats": (_Z, [_I, _I, _I, _I]),
     "bmp_readout_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _P, _P]),
+    "bmp_layer_agg_ws_floats": (_Z, [_I, _I, _I]),
+    "bmp_layer_agg_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "bmp_layer_agg_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _Z, _P]),
     "bmp_linear_fwd": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P]),
     "bmp_wgrad_ws_floats_c": (_Z, [_I, _I, _I]),
     "bmp_linear_wgrad": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),

@@ -1066,3 +1066,97 @@ class NFPReadoutFn(Function):
             check(L.bmp_nfp_readout_bwd(ptr(dg), ptr(h), ptr(s), pb.n_tiles, d, o, ptr(Wnat), ptr(pb.row_w), ptr(pb.row_mol), ptr(dh),
                                         ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_nfp_readout_bwd")
         return dh, dWT, db, None, (dg if ctx.has_prev else None), None
+
+
+# ---------------------------------------------------------------------------------------------------------
+# GGNN layer aggregators (models/ggnn.py:407-579): y = max_t h_t ('max-pool') or sum_s softmax_s(W x + b)_s h_s ('attn',
+# W = attn_dense_layer.W [T x T] over the LAYER axis), per row and channel of the T step outputs.
+# ---------------------------------------------------------------------------------------------------------
+AGG_MODE = {"max-pool": 0, "attn": 1}
+AGG_MAX_T = 8            # step tensors one launch takes (their addresses travel in the kernel arguments)
+
+
+def _agg_check(hs, mode, W, b):
+    if mode not in (0, 1):
+        raise ValueError(f"layer aggregator mode must be 0 (max-pool) or 1 (attn), got {mode!r}")
+    T = len(hs)
+    if not 1 <= T <= AGG_MAX_T:
+        raise ValueError(f"layer aggregator: 1 <= n_layers <= {AGG_MAX_T}, got {T}")
+    N, d = require_rows(hs[0], "agg: h[0]").shape
+    if d % 4:
+        raise ValueError("layer aggregator: the row width must be a multiple of 4")
+    for t in range(1, T):
+        if require_rows(hs[t], f"agg: h[{t}]", d).shape[0] != N:
+            raise ValueError("layer aggregator: the step tensors differ in their row count")
+    if mode == 1:
+        if W is None or tuple(W.shape) != (T, T) or W.dtype != torch.float32 or not W.is_contiguous():
+            raise ValueError(f"layer aggregator: W must be a contiguous float32 ({T}, {T}) tensor")
+        if b is not None and (tuple(b.shape) != (T,) or not b.is_contiguous()):
+            raise ValueError(f"layer aggregator: b must be a contiguous ({T},) tensor")
+    return T, N, d
+
+
+def _agg_fwd(hs, mode, W, b, keep):
+    """y and, when a backward follows, the max form's tie masks (one byte per element).  The attn form keeps nothing:
+    its backward recomputes the softmax from the step tensors it has to read anyway."""
+    T, N, d = _agg_check(hs, mode, W, b)
+    y = torch.empty(N, d, dtype=torch.float32, device=hs[0].device)
+    aux = torch.empty(N * d, dtype=torch.uint8, device=y.device) if (mode == 0 and keep) else None
+    check(_lib.lib().bmp_layer_agg_fwd(_ptr_array(hs), T, N, d, mode, ptr(W), ptr(b), ptr(y), ptr(aux), stream()),
+          "bmp_layer_agg_fwd")
+    return y, aux
+
+
+def _agg_bwd(dy, hs, mode, W, b, aux, dW, db, acc):
+    L = _lib.lib()
+    T, (N, d) = len(hs), hs[0].shape
+    dy = dy.contiguous()
+    dhs = [torch.empty_like(hs[0]) for _ in range(T)]
+    nws = L.bmp_layer_agg_ws_floats(N, d, T) if mode == 1 else 0
+    ws = _ws(nws, dy.device) if mode == 1 else None
+    check(L.bmp_layer_agg_bwd(ptr(dy), _ptr_array(hs) if mode == 1 else None, T, N, d, mode, ptr(W), ptr(b), ptr(aux),
+                              _ptr_array(dhs), ptr(dW), ptr(db), acc, ptr(ws), nws, stream()), "bmp_layer_agg_bwd")
+    return dhs
+
+
+class LayerAggFn(Function):
+    """layer_aggregation's 'max-pool' / 'attn' (models/ggnn.py:424-432, 551-571) of the step outputs ``hs``; ``mode`` from
+    AGG_MODE, W [T x T] and b [T] of attn_dense_layer (None for max-pool)."""
+
+    @staticmethod
+    def forward(ctx, mode, W, b, *hs):
+        y, aux = _agg_fwd(hs, mode, W, b, any(ctx.needs_input_grad))
+        ctx.save_for_backward(*hs)
+        ctx.mode, ctx.W, ctx.b, ctx.aux = mode, W, b, aux
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        hs, mode, W = ctx.saved_tensors, ctx.mode, ctx.W
+        dW = torch.empty_like(W) if mode == 1 else None
+        db = torch.empty_like(ctx.b) if (mode == 1 and ctx.b is not None) else None
+        dhs = _agg_bwd(dy, hs, mode, W, ctx.b, ctx.aux, dW, db, 0)
+        return (None, dW, db, *dhs)
+
+
+class PLayerAggFn(Function):
+    """LayerAggFn on prepared weights (bmp/plan.py).  W: W, b (attn; unused for max-pool); G: dW, db."""
+
+    @staticmethod
+    def forward(ctx, mode, W, G, state, *hs):
+        Wt, bt = (W["W"], W["b"]) if mode == 1 else (None, None)
+        y, aux = _agg_fwd(hs, mode, Wt, bt, any(ctx.needs_input_grad))
+        ctx.save_for_backward(*hs)
+        ctx.mode, ctx.W, ctx.b, ctx.G, ctx.state, ctx.aux = mode, Wt, bt, G, state, aux
+        if mode == 1:
+            _register(state, "agg")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        hs, mode, G = ctx.saved_tensors, ctx.mode, ctx.G
+        acc = 0
+        if mode == 1:
+            acc = 0 if _first_write(ctx.state, "agg") else 1        # the encoder called once per side: the second call adds
+        dhs = _agg_bwd(dy, hs, mode, ctx.W, ctx.b, ctx.aux, G["dW"] if mode == 1 else None, G["db"] if mode == 1 else None, acc)
+        return (None, None, None, None, *dhs)

@@ -2,8 +2,9 @@
 
 Mirrors ``models.ggnn.GGNN`` (models/ggnn.py:19-654) and ``models.ggnn_att.GGNN``
 (models/ggnn_att.py:39-664, which adds ``self.atoms`` / ``get_atom_array()``) on the default
-path: message_function='matrix_multiply', readout_function='graph_level', no attention, no
-layer aggregator, no context BiLSTM, no batch normalisation.  Any other option
+path: message_function='matrix_multiply', readout_function='graph_level', no attention, no context BiLSTM, no batch
+normalisation, plus the closed-form layer aggregators 'concat', 'max-pool' and 'attn' (models/ggnn.py:154-213, 407-579:
+the T step outputs of an atom, combined per channel, go to the readout in the last step's place).  Any other option
 raises NotImplementedError (they are research ablations outside SURVEY.md section 8).
 
 ``dropout_rate`` (models/ggnn.py:626-627): identity under ``eval()``; in training the zero-padded positions of a molecule
@@ -28,6 +29,8 @@ from .packed import PackedMolBatch, pack_from_dense
 
 MAX_ATOMIC_NUM = 117      # chainer_chemistry.config.MAX_ATOMIC_NUM (models/ggnn.py:14)
 NUM_EDGE_TYPE = 4         # models/ggnn.py:37
+LAYER_AGGREGATORS = ('concat', 'max-pool', 'attn')                               # models/ggnn.py:168-198, 407-432, 551-571
+RECURRENT_AGGREGATORS = ('gru', 'lstm', 'gru-attn', 'lstm-attn', 'self-attn')    # :434-549, 573-577: refused
 
 
 class Linear(nn.Module):
@@ -232,11 +235,21 @@ class GGNN(nn.Module):
                  num_output_hidden_layers=0, output_hidden_dim=16, output_activation=None,
                  output_atoms=False):
         super().__init__()
-        unsupported = dict(layer_aggregator=layer_aggregator, batch_normalization=batch_normalization,
+        unsupported = dict(batch_normalization=batch_normalization,
                            use_attention=use_attention, update_attention=update_attention, context=context)
         for k, v in unsupported.items():
             if v:
                 raise NotImplementedError(f"GGNN option {k}={v!r} is outside the MI355X hot path (SURVEY.md 2.1 #1)")
+        if layer_aggregator:
+            if layer_aggregator in RECURRENT_AGGREGATORS:
+                raise NotImplementedError(
+                    f"layer_aggregator={layer_aggregator!r} rests on Chainer's cuDNN-form NStepBiGRU / NStepBiLSTM (or, for "
+                    "'self-attn', on a branch the reference leaves empty): their arithmetic is not in the reference tree")
+            if layer_aggregator not in LAYER_AGGREGATORS:
+                raise ValueError('There is no such layer aggregator named {}'.format(layer_aggregator))
+            if layer_aggregator != 'concat' and not 1 <= n_layers <= Fn.AGG_MAX_T:
+                raise ValueError(f"layer_aggregator={layer_aggregator!r} takes 1 <= n_layers <= {Fn.AGG_MAX_T}")
+        self.layer_aggregator = layer_aggregator or None
         if not 0.0 <= dropout_rate < 1.0:
             raise ValueError("dropout_rate must lie in [0, 1)")
         self.dropout_rate = dropout_rate        # models/ggnn.py:626-627; see forward()
@@ -258,26 +271,46 @@ class GGNN(nn.Module):
         self.message_layers = nn.ModuleList(
             [Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
         self.update_layer = GRU(2 * hidden_dim, hidden_dim)
-        self.i_layers = nn.ModuleList([Linear(2 * hidden_dim, out_dim) for _ in range(self.n_readout_layer)])
-        self.j_layers = nn.ModuleList([Linear(hidden_dim, out_dim) for _ in range(self.n_readout_layer)])
+        # construct_layer_aggregator (models/ggnn.py:168-213): 'concat' reads the T step outputs side by side
+        ro_dim = n_layers * hidden_dim if self.layer_aggregator == 'concat' else hidden_dim
+        self.i_layers = nn.ModuleList([Linear(2 * ro_dim, out_dim) for _ in range(self.n_readout_layer)])
+        self.j_layers = nn.ModuleList([Linear(ro_dim, out_dim) for _ in range(self.n_readout_layer)])
+        if self.layer_aggregator == 'attn':
+            # Linear(n_layers, n_layers) over the LAYER axis (:163-164).  The reference's always-true tests also create a
+            # BiGRU and a BiLSTM nobody calls: not here
+            self.attn_dense_layer = Linear(n_layers, n_layers)
         self.atoms = None
         self.fused = True      # use the fused per-tile step kernel where the width allows (64, 128)
 
     # models/ggnn.py:333-341: i sees [h, h0], j sees h only -> j's h0 rows are zero in the kernel layout
     def _readout_weights(self, k: int):
         i, j = self.i_layers[k], self.j_layers[k]
-        d = self.hidden_dim
+        d = j.W.shape[1]                  # hidden_dim; n_layers * hidden_dim under layer_aggregator='concat'
         WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
         return WT.contiguous(), torch.cat((i.b, j.b))
 
     def readout(self, h, h0, pb, step=0):
-        k = step if self.concat_hidden else 0
+        k = step if (self.concat_hidden and not self.layer_aggregator) else 0
         WT, b = self._readout_weights(k)
         return Fn.ReadoutFn.apply(h, h0, WT, b, pb, Fn.ACT["identity"])
 
     # ---- layout plan protocol (bmp/plan.py): the weight-layout code above as pure functions of the parameters ----
     def plannable(self) -> bool:
-        return self.fused and not self.concat_hidden and self.dropout_rate == 0.0
+        return self.fused and not self.concat_hidden and self.dropout_rate == 0.0 and self.layer_aggregator != 'concat'
+
+    def aggregate(self, hs, h0, fast=None):
+        """layer_aggregation (models/ggnn.py:407-579) up to the readout: (what the readout reads in h's place, its h0)."""
+        agg = self.layer_aggregator
+        if agg == 'concat':                                   # :415-422
+            return torch.cat(hs, dim=1), torch.cat([h0] * len(hs), dim=1)
+        mode = Fn.AGG_MODE[agg]
+        if fast is not None:
+            P, G, state, _tape = fast
+            W = dict(W=P["agg.W"], b=P["agg.b"]) if mode == 1 else None
+            Gd = dict(dW=G["agg.dW"], db=G["agg.db"]) if mode == 1 else None
+            return Fn.PLayerAggFn.apply(mode, W, Gd, state, *hs), h0
+        lin = getattr(self, "attn_dense_layer", None)
+        return Fn.LayerAggFn.apply(mode, None if lin is None else lin.W, None if lin is None else lin.b, *hs), h0
 
     # d = 32 (the reference's published width) has fused step kernels of its own (csrc/bmp_fused_small.hip); ``fused_small =
     # False`` sends that width through the unfused operators again (bench.py's A/B of the two, tests)
@@ -299,9 +332,17 @@ class GGNN(nn.Module):
             out[f"gru_{mode}.AT"], UcT, out[f"gru_{mode}.b"] = self.update_layer.kernel_weights(first=(mode == "first"))
         out["gru.UcT"] = UcT
         out["ro.WT"], out["ro.b"] = self._readout_weights(0)
+        if self.layer_aggregator == 'attn':
+            out["agg.W"], out["agg.b"] = self.attn_dense_layer.W, self.attn_dense_layer.b
         return out
 
     def prepared_layouts(self):
+        out = self._prepared_layouts()
+        if self.layer_aggregator == 'attn':          # the kernel reads attn_dense_layer in the reference's own layout
+            out["agg.W"], out["agg.b"] = self.attn_dense_layer.W, self.attn_dense_layer.b
+        return out
+
+    def _prepared_layouts(self):
         p = self.primary_layouts()
         if not self._plan_fused():          # unfused operators: K-major operands and their transposes, nothing packed
             out = {"embed.W": p["embed.W"], "gru.UcT": p["gru.UcT"], "gru.Uc": p["gru.UcT"].t().contiguous(),
@@ -328,6 +369,8 @@ class GGNN(nn.Module):
     def gk_spec(self):
         d, o = self.hidden_dim, self.out_dim
         spec = {"embed.dW": tuple(self.embed.W.shape), "ro.dWT": (2 * d, 2 * o), "ro.db": (2 * o,)}
+        if self.layer_aggregator == 'attn':
+            spec["agg.dW"], spec["agg.db"] = (self.n_layers, self.n_layers), (self.n_layers,)
         if not self._plan_fused():
             for li in range(self.n_message_layer):
                 spec[f"msg{li}.dWT"], spec[f"msg{li}.dbE"] = (4 * d, d), (4, d)
@@ -342,6 +385,12 @@ class GGNN(nn.Module):
     def primary_grads(self, gk):
         """Gradients of the primary layouts as lists of terms taken from the kernels' buffers (the same slicing
         GGNNStepFn.backward does)."""
+        out = self._primary_grads(gk)
+        if self.layer_aggregator == 'attn':
+            out["agg.W"], out["agg.b"] = [gk["agg.dW"]], [gk["agg.db"]]
+        return out
+
+    def _primary_grads(self, gk):
         d = self.hidden_dim
         groups = list(dict.fromkeys(self._step_groups()))
         if not self._plan_fused():
@@ -370,7 +419,8 @@ class GGNN(nn.Module):
         """The encoder on the plan's prepared weights: embed, fused steps, readout -- no layout work, no weight
         gradients through autograd."""
         h, h0 = self._encode_fast(pb, fast, h_in)
-        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+        # with an aggregator the reference returns before ``self.atoms = h`` (models/ggnn_att.py:648-651)
+        self.atoms = None if self.layer_aggregator else PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
         return self._readout_fast(h, h0, pb, fast)
 
     def _readout_fast(self, h, h0, pb, fast):
@@ -385,7 +435,15 @@ class GGNN(nn.Module):
                                    getattr(self, "_readout_off_chain", False), infer)
 
     def _encode_fast(self, pb, fast, h_in=None):
-        """embed + propagation steps on the plan's prepared weights: (h after the last step, h0)."""
+        """embed + propagation steps on the plan's prepared weights: (h after the last step -- with a layer aggregator what
+        it makes of all the steps' outputs --, h0)."""
+        hs = [] if self.layer_aggregator else None
+        h, h0 = self._steps_fast(pb, fast, h_in, hs)
+        if hs is not None:
+            h, h0 = self.aggregate(hs, h0, fast)
+        return h, h0
+
+    def _steps_fast(self, pb, fast, h_in, hs):
         P, G, state, tape = fast
         if h_in is None:
             pb.check_atom_ids(P["embed.W"].shape[0])
@@ -400,6 +458,8 @@ class GGNN(nn.Module):
                 Wg = dict(AT=P[f"gru_{mode}.AT"], UcT=P["gru.UcT"], b=P[f"gru_{mode}.b"], A=P[f"gru_{mode}.A"], Uc=P["gru.Uc"])
                 Gg = dict(dAT=G[f"gru_{mode}.dAT"], dUcT=G[f"gru_{mode}.dUcT"], db=G[f"gru_{mode}.db"])
                 h = Fn.PGRUFn.apply(h, m, pb, Wg, Gg, state, f"gru_{mode}", step == 0)
+                if hs is not None:
+                    hs.append(h)
             Fn._join_parts(state)             # the steps ran as two chains of tiles
             return h, h0
         # every step's outputs first, then the two chains of tiles are opened ONCE (Fn.fork_parts) and run to the join
@@ -422,13 +482,16 @@ class GGNN(nn.Module):
         per_step = per_step[1]
         for step, (W, Gs, g, first) in enumerate(per_step):
             h = Fn.PStepFn.apply(h, pb, W, Gs, state, g, first, bufs[step])
+            if hs is not None:
+                hs.append(h)
         Fn._join_parts(state)                 # the steps ran as two chains of tiles: whole arrays are read from here on
         return h, h0
 
     def encode_rows(self, pb: PackedMolBatch):
         """embed + the propagation steps (models/ggnn.py:599-627) WITHOUT the readout: (h, h0) on the rows of ``pb`` -- the
         entry the pair predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the
-        per-instance rows (``readout_rows``)."""
+        per-instance rows (``readout_rows``).  With a layer aggregator ``h`` is the aggregate of the step outputs (and, for
+        'concat', h0 its T-fold repetition): per row and channel, so it commutes with the copy to the instance rows."""
         if self.concat_hidden or (self.dropout_rate != 0.0 and self.training):
             raise NotImplementedError("encode_rows: concat_hidden / training dropout take the per-instance batch form")
         fast = getattr(self, "_fast", None)
@@ -439,6 +502,7 @@ class GGNN(nn.Module):
         h0 = h
         fused = self.fused and self._plan_fused() and not pb.oversized
         later, msgw, cache = None, {}, {}
+        hs = []
         for step in range(self.n_layers):
             li = 0 if self.weight_tying else step
             if li not in msgw:
@@ -455,6 +519,9 @@ class GGNN(nn.Module):
             else:
                 m = Fn.MsgFn.apply(h, WT, bE, None, None, pb, Fn.ACT["identity"])
                 h = Fn.GRUFn.apply(h, m, AT, UcT, b, pb, step == 0)
+            hs.append(h)
+        if self.layer_aggregator:
+            return self.aggregate(hs, h0)
         return h, h0
 
     def readout_rows(self, h, h0, pb: PackedMolBatch):
@@ -493,7 +560,8 @@ class GGNN(nn.Module):
         fused = self.fused and self._plan_fused() and not drop and not big
         state, state_w = None, None           # dropout: the GRU's own (un-dropped) state and its unfolded weights
         masks = getattr(self, "_dropout_masks", None)      # tests inject the masks (one (n_rows, d) tensor per step)
-        g_list = []
+        g_list, hs = [], []
+        agg = self.layer_aggregator
         msgw, cache = {}, {}          # per-call: kernel-layout weights of each layer, packed copies
         for step in range(self.n_layers):                               # :616
             li = 0 if self.weight_tying else step                       # :220
@@ -523,8 +591,13 @@ class GGNN(nn.Module):
             else:
                 m = Fn.MsgFn.apply(h, WT, bE, None, None, pb, Fn.ACT["identity"])
                 h = Fn.GRUFn.apply(h, m, AT, UcT, b, pb, step == 0)    # :254-262, state reset at :599
-            if self.concat_hidden:
+            if agg:                     # :637-639 (with concat_hidden as well the reference computes the per-step readouts and
+                hs.append(h)            #  throws them away: skipped)
+            elif self.concat_hidden:
                 g_list.append(self.readout(h, h0, pb, step))
+        if agg:                         # :643-644; models/ggnn_att.py:648-651 returns before ``self.atoms = h``
+            self.atoms = None
+            return self.readout(*self.aggregate(hs, h0), pb, 0)
         self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)     # models/ggnn_att.py:651
         if self.concat_hidden:
             return torch.cat(g_list, dim=1)
@@ -532,5 +605,9 @@ class GGNN(nn.Module):
 
     def get_atom_array(self):
         """models/ggnn_att.py:662-664.  Returns a PackedAtoms; ``.dense()`` gives (mb, A, hidden_dim)."""
+        if self.atoms is None and self.layer_aggregator:
+            raise RuntimeError(f"get_atom_array(): with layer_aggregator={self.layer_aggregator!r} the encoder keeps no atom "
+                               "array (the reference returns before it is set, models/ggnn_att.py:648-651), so a "
+                               "co-attention has nothing to read")
         assert self.atoms is not None
         return self.atoms

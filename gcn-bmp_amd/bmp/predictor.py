@@ -45,7 +45,8 @@ class GraphConvPredictorForPair(nn.Module):
             h, h0 = self.graph_conv.encode_rows(eb.pb_enc)
             rows = EncRowsFn.apply(h, eb)
             rows0 = None if h0 is None else EncRowsFn.apply(h0, eb)
-            at = PackedAtoms(rows, eb.pb, None)
+            # (an encoder with a layer aggregator hands over no atom array: models/ggnn_att.py:648-651)
+            at = None if getattr(self.graph_conv, "layer_aggregator", None) else PackedAtoms(rows, eb.pb, None)
             self.graph_conv.atoms = at
             g = self.graph_conv.readout_rows(rows, rows0, eb.pb)
             B = eb.pb.side_mols[1]
@@ -53,14 +54,22 @@ class GraphConvPredictorForPair(nn.Module):
         if isinstance(atoms_1, PackedMolBatch) and len(atoms_1.side_mols) == 3 and atoms_2 is None:
             pb = atoms_1
             g = self.graph_conv(pb)
-            at = self.graph_conv.get_atom_array()
+            at = self._atoms()
             B = pb.side_mols[1]
             return g[:B], g[B:], at, at, (0, B)
         g1 = self.graph_conv(atoms_1, adjs_1)
-        at1 = self.graph_conv.get_atom_array()
+        at1 = self._atoms()
         g2 = self.graph_conv(atoms_2, adjs_2)
-        at2 = self.graph_conv.get_atom_array()
+        at2 = self._atoms()
         return g1, g2, at1, at2, (0, 0)
+
+    def _atoms(self):
+        """The encoder's atom array for the co-attention (train_binary.py:93,95).  Without a co-attention nobody reads it, and
+        an encoder with a layer aggregator has none to give: asked for only when it is used, so that such an encoder works
+        with a plain link predictor and fails with get_atom_array()'s message under a co-attention."""
+        if self.attn is None and getattr(self.graph_conv, "layer_aggregator", None):
+            return None
+        return self.graph_conv.get_atom_array()
 
     def forward(self, atoms_1, adjs_1=None, atoms_2=None, adjs_2=None):
         return self._forward(atoms_1, adjs_1, atoms_2, adjs_2, None)

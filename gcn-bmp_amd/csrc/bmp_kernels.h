@@ -111,6 +111,18 @@ int bmp_launch_gather_bwd(const float* dagg, int N, int d, const int* ptrT, cons
                           float* dx, int lddx, int accumulate, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
+// Layer aggregators (bmp_agg.hip): bmp_layer_agg_fwd / _bwd / _ws_floats of include/bmp.h
+// ---------------------------------------------------------------------------------------------
+#define BMP_AGG_MAXT 8               // step tensors per launch: their pointers travel by value in the kernel arguments
+enum { BMP_AGG_MAX = 0, BMP_AGG_ATTN = 1 };
+extern "C" size_t bmp_layer_agg_ws_floats(int n_rows, int d, int T);
+extern "C" int bmp_layer_agg_fwd(const float* const* h, int T, int n_rows, int d, int mode, const float* W, const float* b,
+                                 float* y, void* aux, hipStream_t st);
+extern "C" int bmp_layer_agg_bwd(const float* dy, const float* const* h, int T, int n_rows, int d, int mode, const float* W,
+                                 const float* b, const void* aux, float* const* dh, float* dW, float* db, int accumulate_w,
+                                 float* ws, size_t ws_floats, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
 // Optional per-kernel-class timing with HIP events (bench.py's roofline leg).  Off by default;
 // the only process-global state in the library.  While a class is armed, every launch of that
 // class is bracketed by two events on the launch stream.

@@ -449,6 +449,25 @@ int bmp_pairfeat_bwd(int kind, const float* dout, const float* x1, const float* 
                      const float* V1, const float* V2, int K, float* dx1, float* dx2, float* dW, float* dV1, float* dV2,
                      float* db, bmp_stream_t stream);
 
+/* ---- GGNN layer aggregators (models/ggnn.py:407-579: layer_aggregation of the T step outputs h_1..h_T, the result goes to
+ * the readout in h's place).  mode 0 'max-pool' (:424-432): y = max_t h_t; mode 1 'attn' (:551-571): per (row, channel)
+ * z_s = sum_t W[s,t] h_t + b_s (attn_dense_layer = Linear(T, T) over the LAYER axis, W [T x T] reference layout, b [T] or
+ * NULL), p = softmax_s(z), y = sum_s p_s h_s.  ('concat' is a concatenation in front of bmp_readout_*.)
+ * h / dh: HOST arrays of T device pointers, each [n_rows x d], 1 <= T <= 8, d % 4 == 0; the pointers travel in the kernel
+ * arguments, so a launch can be captured.  Elementwise over n_rows x d: no row weights, dead and pad rows are rows.
+ * aux (may be NULL in the forward when no backward follows): max: n_rows * d BYTES, the T-bit mask of the positions equal
+ * to the maximum -- the backward hands the whole dy to every one of them (chainer's F.max) and REQUIRES it; attn: T * n_rows
+ * * d floats of p, or NULL -- the backward then recomputes p from h, W and b (the form the library's callers use, see
+ * DESIGN.md).  The backward writes every dh_t whole; dW [T x T] / db [T] (attn; db may be NULL) are reduced over all rows
+ * and channels in a fixed order (bit-identical from run to run) through ws of bmp_layer_agg_ws_floats floats;
+ * accumulate_w != 0 adds into them. */
+size_t bmp_layer_agg_ws_floats(int n_rows, int d, int T);
+int bmp_layer_agg_fwd(const float* const* h, int T, int n_rows, int d, int mode, const float* W, const float* b, float* y,
+                      void* aux, bmp_stream_t stream);
+int bmp_layer_agg_bwd(const float* dy, const float* const* h, int T, int n_rows, int d, int mode, const float* W,
+                      const float* b, const void* aux, float* const* dh, float* dW, float* db, int accumulate_w, float* ws,
+                      size_t ws_floats, bmp_stream_t stream);
+
 /* ---- host glue of a training step (no counterpart kernels in the reference: there the layout changes are Chainer
  * function nodes and the optimizer is chainer.optimizers.Adam, train_ddi_modify.py:289) ----
  * bmp_gather_sum: dst[i] (=|+=) sum_k src[idx[k*n + i]] over table entries >= 0 (idx is [K][n] int32).  One launch
