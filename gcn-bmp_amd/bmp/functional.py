@@ -1069,6 +1069,98 @@ class NFPReadoutFn(Function):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Graph isomorphism network layer (models/gin.py:89-128; csrc/bmp_gin.hip).
+# ---------------------------------------------------------------------------------------------------------
+GIN_PATHS = {"fused": 0, "composed": 0}          # forward calls per form
+
+
+def gin_tile_ok(pb) -> bool:
+    """The fused GIN kernels take whole 128-row tiles whose molecules never straddle a tile."""
+    return pb.mt_row0 is None and not pb.oversized
+
+
+def gin_layer_supported(d: int) -> bool:
+    return bool(_lib.lib().bmp_gin_layer_supported(int(d)))
+
+
+def _linear_wgrad(X, dY):
+    """(dWT [K x Nout], db [Nout]) = (X^T dY, column sums of dY): the row-GEMM weight-gradient entry (deterministic)."""
+    L = _lib.lib()
+    N, K = X.shape
+    Nout = dY.shape[1]
+    dWT = torch.empty(K, Nout, dtype=torch.float32, device=X.device)
+    db = torch.empty(Nout, dtype=torch.float32, device=X.device)
+    nws = L.bmp_wgrad_ws_floats_c(N, K, Nout)
+    ws = _ws(nws, X.device)
+    check(L.bmp_linear_wgrad(ptr(X), K, ptr(dY), Nout, N, K, Nout, ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_linear_wgrad")
+    return dWT, db
+
+
+class GinLayerFn(Function):
+    """GINUpdate.__call__ (models/gin.py:89-128) as ONE fused kernel per tile and direction: out = relu(keep * (relu(s . W1T + b1)
+    . W2T + b2)), s = h + the type-blind neighbour sum.  W1T / W2T [d x d] K-major (the transposed Linear weights), keep [N x d]
+    (0 or 1 / (1 - p)) or None.  d in {64, 128}, whole tiles (gin_tile_ok); the other shapes go through ``gin_layer``."""
+
+    @staticmethod
+    def forward(ctx, x, W1T, b1, W2T, b2, keep, pb):
+        L = _lib.lib()
+        require_rows(x, "gin layer: x")
+        _check_pb(pb, x)
+        N, d = x.shape
+        if tuple(W1T.shape) != (d, d) or tuple(W2T.shape) != (d, d) or tuple(b1.shape) != (d,) or tuple(b2.shape) != (d,):
+            raise ValueError("gin layer: weight shapes do not match x")
+        if not (gin_tile_ok(pb) and gin_layer_supported(d)):
+            raise ValueError("gin layer: the fused kernels take d in {64, 128} on whole tiles; use gin_layer()")
+        if keep is not None:
+            require_rows(keep, "gin layer: keep", d)
+            if keep.shape[0] != N:
+                raise ValueError("gin layer: keep must have one row per packed row")
+        b1, b2 = b1.contiguous(), b2.contiguous()
+        W1p, W2p = pack_k4(W1T), pack_k4(W2T)
+        f = lambda: torch.empty(N, d, dtype=torch.float32, device=x.device)
+        s, t, out = f(), f(), f()
+        check(L.bmp_gin_layer_tile_fwd(ptr(x), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(W1p), ptr(b1),
+                                       ptr(W2p), ptr(b2), ptr(keep), ptr(s), ptr(t), ptr(out), stream()), "bmp_gin_layer_tile_fwd")
+        ctx.save_for_backward(W1T, W2T, s, t, out, keep if keep is not None else torch.empty(0))
+        ctx.pb, ctx.has_keep = pb, keep is not None
+        GIN_PATHS["fused"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        W1T, W2T, s, t, out, keep = ctx.saved_tensors
+        pb = ctx.pb
+        keep = keep if ctx.has_keep else None
+        dout = dout.contiguous()
+        N, d = s.shape
+        W2np, W1np = pack_k4(W2T.t()), pack_k4(W1T.t())
+        f = lambda: torch.empty(N, d, dtype=torch.float32, device=s.device)
+        dp2, dp1, dh = f(), f(), f()
+        check(L.bmp_gin_layer_tile_bwd(ptr(dout), ptr(out), ptr(keep), ptr(t), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
+                                       ptr(pb.csrT_val), ptr(W2np), ptr(W1np), ptr(dp2), ptr(dp1), ptr(dh), stream()),
+              "bmp_gin_layer_tile_bwd")
+        dW2T, db2 = _linear_wgrad(t, dp2)
+        dW1T, db1 = _linear_wgrad(s, dp1)
+        return dh, dW1T, db1, dW2T, db2, None, None
+
+
+def gin_layer(x, W1T, b1, W2T, b2, keep, pb, fused=True):
+    """One GIN layer.  The fused kernels where the tensors are on the GPU, the width is supported and no molecule spans tiles;
+    otherwise the existing operators, for any width that is a multiple of 8: the message operator with W1 for each of the four
+    bond types, no per-type bias and the self connection (W1, b1) under relu -- relu((sum_e agg_e + h) . W1T + b1) --, then the
+    row linear with relu (with a dropout mask: identity, the mask, relu).  Both are differentiable through autograd."""
+    d = x.shape[1]
+    if fused and x.is_cuda and gin_tile_ok(pb) and gin_layer_supported(d):
+        return GinLayerFn.apply(x, W1T, b1, W2T, b2, keep, pb)
+    GIN_PATHS["composed"] += 1
+    t = MsgFn.apply(x, W1T.repeat(4, 1), torch.zeros(4, d, dtype=x.dtype, device=x.device), W1T, b1, pb, ACT["relu"])
+    if keep is None:
+        return LinearRowsFn.apply(t, W2T, b2, ACT["relu"])
+    return torch.relu(LinearRowsFn.apply(t, W2T, b2, ACT["identity"]) * keep)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # GGNN layer aggregators (models/ggnn.py:407-579): y = max_t h_t ('max-pool') or sum_s softmax_s(W x + b)_s h_s ('attn',
 # W = attn_dense_layer.W [T x T] over the LAYER axis), per row and channel of the T step outputs.
 # ---------------------------------------------------------------------------------------------------------

@@ -29,7 +29,8 @@ class GraphConvPredictorForPair(nn.Module):
         # (or, without one, the encoder) hands over per molecule -- so the parameters exist before an optimizer flattens them.
         fp = getattr(attn if attn is not None else graph_conv, "out_dim", None)
         if attn is None and getattr(graph_conv, "concat_hidden", False):
-            fp = fp * graph_conv.n_layers                                   # models/ggnn.py:646-647
+            # models/ggnn.py:646-647; GIN concatenates one readout per layer that RAN (models/gin.py:215-223: n_concat)
+            fp = fp * getattr(graph_conv, "n_concat", graph_conv.n_layers)
         if fp is not None and callable(getattr(mlp, "materialize_input", None)):
             mlp.materialize_input(int(fp))
 
@@ -147,8 +148,9 @@ def build_link_predictor(sim_method: str, fp_out_dim: int, class_num: int, net_h
 
 
 def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=True, attn: Optional[str] = "nie",
-                         head=8, class_num=1, encoder="ggnn", mlp_hidden=(32, 16), sim_method="mlp"):
-    """set_up_predictor counterpart (train_binary.py:144-277) for the configs of BASELINE.json."""
+                         head=8, class_num=1, encoder="ggnn", mlp_hidden=(32, 16), sim_method="mlp", dropout_ratio=0.5):
+    """set_up_predictor counterpart (train_binary.py:144-277) for the configs of BASELINE.json.  ``dropout_ratio``: the GIN
+    encoder's (the trainer builds it with 0.5); the other encoders do not read it."""
     if encoder == "ggnn":
         enc = GGNN(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
     elif encoder == "relgcn":
@@ -157,6 +159,11 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
     elif encoder == "nfp":                                                       # train_binary.py:274-276
         from .nfp import NFP
         enc = NFP(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers)
+    elif encoder == "gin":                                                       # train_ggnn_hole_multi_class_x37.py:226-228
+        from .gin import GIN
+        # the trainer does not hand its weight-tying option to GIN: tied (ONE layer runs) unless asked for by keyword here
+        enc = GIN(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, dropout_ratio=dropout_ratio, concat_hidden=True,
+                  weight_tying=weight_tying)
     else:
         raise ValueError('[ERROR] Invalid graph embedding encoder.')
     a = None
@@ -194,5 +201,6 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
         a = NeuralCoattention(hidden_dim=hidden_dim, out_dim=out_dim, activation="tanh")
     elif attn is not None:
         raise ValueError('[ERROR] Invalid Co-Attention Method.')
-    fp_dim = getattr(a, "out_dim", out_dim) if a is not None else out_dim        # BiMPM hands over 3 * head columns
+    # BiMPM hands over 3 * head columns; without a co-attention GIN hands over one readout per layer that ran
+    fp_dim = getattr(a, "out_dim", out_dim) if a is not None else out_dim * getattr(enc, "n_concat", 1)
     return GraphConvPredictorForPair(enc, a, build_link_predictor(sim_method, fp_dim, class_num, mlp_hidden))

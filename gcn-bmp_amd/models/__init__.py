@@ -4,3 +4,4 @@ reference's trainer scripts find the MI355X-native operators under the names the
 from bmp.ggnn import GGNN                       # noqa: F401
 from bmp.relgcn import RelGCN                   # noqa: F401
 from bmp.mlp import MLP                         # noqa: F401
+from bmp.gin import GIN                         # noqa: F401

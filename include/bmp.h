@@ -190,6 +190,25 @@ int bmp_relgcn_layer_wgrad(const float* h, const float* wdeg, const float* gda, 
                            float* cs, int accumulate, const int* type_rows, const int* type_cnt, float* ws, size_t ws_floats,
                            bmp_stream_t stream);          /* type_rows / type_cnt: as bmp_ggnn_step_wgrad */
 
+/* ---- Graph isomorphism network (GIN) layer -- models/gin.py:89-128 (csrc/bmp_gin.hip) ----
+ * s = h + sum over the forward CSR of val * h[csr_col >> 2] (the adjacency summed over the bond types, every entry with its
+ * value); t = relu(s . W1^T + b1); out = relu(keep * (t . W2^T + b2)).  keep [N x d]: the dropout mask between the second linear
+ * and its relu, 0 or 1 / (1 - p) per element; a null pointer means no dropout.  Nothing is masked by row.
+ * One kernel per direction, one workgroup per 128-row tile, d with bmp_gin_layer_supported (64 or 128), exact-f32 MFMA; whole
+ * tiles whose molecules never straddle a tile (no tile table).  N = 128 n_tiles.
+ * fwd: W1p / W2p [d x d] = W1^T / W2^T (K-major) K4-packed as for bmp_ggnn_step_*; saves s and t [N x d] and writes out [N x d].
+ * bwd: W2np / W1np [d x d] = W2 / W1 in the reference layout [out x in], K4-packed; writes dp2 = dout * [out > 0] * keep,
+ * dp1 = (dp2 . W2) * [t > 0] and dh = ds + transposed-CSR gather of ds, ds = dp1 . W1 (all [N x d]).
+ * Weight gradients: dW2^T = t^T dp2, db2 = column sums of dp2, dW1^T = s^T dp1, db1 = column sums of dp1 -- two calls of
+ * bmp_linear_wgrad (deterministic, no atomics).  No allocation, no host sync; every row array 16-byte aligned. */
+int bmp_gin_layer_supported(int d);
+int bmp_gin_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                           const float* W1p, const float* b1, const float* W2p, const float* b2, const float* keep, float* s,
+                           float* t, float* out, bmp_stream_t stream);
+int bmp_gin_layer_tile_bwd(const float* dout, const float* out, const float* keep, const float* t, int n_tiles, int d,
+                           const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* W2np, const float* W1np,
+                           float* dp2, float* dp1, float* dh, bmp_stream_t stream);
+
 /* ---- Neural-fingerprint encoder -- models/models/nfp.py (csrc/bmp_nfp.hip) ----
  * ONE adjacency: every bond counts once whatever its type (csr_col >> 2 is the source row), plus a self loop of weight
  * self_w [N] on the rows that have one (1 on real atoms, 0 on pad and dead rows).  deg_class [N] in 0..7: k when the COLUMN
