@@ -418,6 +418,20 @@ class ReadoutFn(Function):
         return dh, dh0, dWT, db, None, None
 
 
+def _linear_wgrad(X, dY, bias=True):
+    """(dWT [K x Nout], db [Nout]) = (X^T dY, column sums of dY): the row-GEMM weight-gradient entry (deterministic).
+    ``bias`` False: no column sums, db is None."""
+    L = _lib.lib()
+    N, K = X.shape
+    Nout = dY.shape[1]
+    dWT = torch.empty(K, Nout, dtype=torch.float32, device=X.device)
+    db = torch.empty(Nout, dtype=torch.float32, device=X.device) if bias else None
+    nws = L.bmp_wgrad_ws_floats_c(N, K, Nout)
+    ws = _ws(nws, X.device)
+    check(L.bmp_linear_wgrad(ptr(X), K, ptr(dY), Nout, N, K, Nout, ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_linear_wgrad")
+    return dWT, db
+
+
 class LinearRowsFn(Function):
     """GraphLinear on packed rows: Y = act(X . WT + b).  X [N x K] with N a multiple of the
     tile size; WT [K x Nout]."""
@@ -464,12 +478,7 @@ class LinearRowsFn(Function):
         dX = torch.empty_like(X)
         check(L.bmp_linear_fwd(ptr(dYp), dYp.shape[1], N // R, dYp.shape[1], K, ptr(Wn), K, None, 0, ptr(dX), K, stream()),
               "bmp_linear_fwd(dX)")
-        dWT = torch.empty_like(WT)
-        db = torch.empty(Nout, dtype=torch.float32, device=X.device) if ctx.has_b else None
-        nws = L.bmp_wgrad_ws_floats_c(N, K, Nout)
-        ws = _ws(nws, X.device)
-        check(L.bmp_linear_wgrad(ptr(X), K, ptr(dY), Nout, N, K, Nout, ptr(dWT), ptr(db), ptr(ws), nws, stream()),
-              "bmp_linear_wgrad")
+        dWT, db = _linear_wgrad(X, dY, ctx.has_b)
         return dX, dWT, db, None
 
 
@@ -935,12 +944,12 @@ class PRelLayerFn(Function):
 # Neural-fingerprint encoder (models/models/nfp.py; csrc/bmp_nfp.hip).  ``nd`` is the batch's derived NFP data
 # (bmp.nfp.nfp_derived): self_w, deg_class, deg_rows, deg_cnt.
 # ---------------------------------------------------------------------------------------------------------
+def whole_tiles_ok(pb) -> bool:
+    """The fused GIN and NFP kernels take whole 128-row tiles whose molecules never straddle a tile."""
+    return pb.mt_row0 is None and not pb.oversized
+
+
 NFP_PATHS = {"layer_tile": 0, "layer_rows": 0, "readout_tile": 0, "readout_rows": 0}      # forward calls per kernel form
-
-
-def nfp_tile_ok(pb) -> bool:
-    """The fused NFP kernels take whole 128-row tiles whose molecules never straddle a tile."""
-    return pb.mt_row0 is None and not pb.oversized and pb.row_mol is not None
 
 
 class NFPLayerFn(Function):
@@ -960,7 +969,8 @@ class NFPLayerFn(Function):
         WT = WT.contiguous(); B = B.contiguous()
         fv = torch.empty(N, d_in, dtype=torch.float32, device=x.device)
         out = torch.empty(N, d_out, dtype=torch.float32, device=x.device)
-        tile = bool(fused) and nfp_tile_ok(pb) and d_in == d_out and bool(L.bmp_nfp_layer_supported(d_in))
+        tile = (bool(fused) and whole_tiles_ok(pb) and pb.row_mol is not None and d_in == d_out
+                and bool(L.bmp_nfp_layer_supported(d_in)))
         if tile:
             WTp = torch.stack([pack_k4(WT[k]) for k in range(7)])
             check(L.bmp_nfp_layer_tile_fwd(ptr(x), pb.n_tiles, d_in, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
@@ -1028,7 +1038,7 @@ class NFPReadoutFn(Function):
                 raise ValueError("nfp readout: g_prev must be a contiguous (n_mols, o) array")
             g = g_prev
             ctx.mark_dirty(g_prev)
-        tile = bool(fused) and nfp_tile_ok(pb) and bool(L.bmp_nfp_readout_tile_supported(d, o))
+        tile = bool(fused) and whole_tiles_ok(pb) and pb.row_mol is not None and bool(L.bmp_nfp_readout_tile_supported(d, o))
         acc = 0 if g_prev is None else 1
         if tile:
             check(L.bmp_nfp_readout_tile_fwd(ptr(h), pb.n_tiles, d, o, ptr(pack_k4(WT)), ptr(b), ptr(pb.row_w), ptr(pb.row_mol),
@@ -1074,32 +1084,14 @@ class NFPReadoutFn(Function):
 GIN_PATHS = {"fused": 0, "composed": 0}          # forward calls per form
 
 
-def gin_tile_ok(pb) -> bool:
-    """The fused GIN kernels take whole 128-row tiles whose molecules never straddle a tile."""
-    return pb.mt_row0 is None and not pb.oversized
-
-
 def gin_layer_supported(d: int) -> bool:
     return bool(_lib.lib().bmp_gin_layer_supported(int(d)))
-
-
-def _linear_wgrad(X, dY):
-    """(dWT [K x Nout], db [Nout]) = (X^T dY, column sums of dY): the row-GEMM weight-gradient entry (deterministic)."""
-    L = _lib.lib()
-    N, K = X.shape
-    Nout = dY.shape[1]
-    dWT = torch.empty(K, Nout, dtype=torch.float32, device=X.device)
-    db = torch.empty(Nout, dtype=torch.float32, device=X.device)
-    nws = L.bmp_wgrad_ws_floats_c(N, K, Nout)
-    ws = _ws(nws, X.device)
-    check(L.bmp_linear_wgrad(ptr(X), K, ptr(dY), Nout, N, K, Nout, ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_linear_wgrad")
-    return dWT, db
 
 
 class GinLayerFn(Function):
     """GINUpdate.__call__ (models/gin.py:89-128) as ONE fused kernel per tile and direction: out = relu(keep * (relu(s . W1T + b1)
     . W2T + b2)), s = h + the type-blind neighbour sum.  W1T / W2T [d x d] K-major (the transposed Linear weights), keep [N x d]
-    (0 or 1 / (1 - p)) or None.  d in {64, 128}, whole tiles (gin_tile_ok); the other shapes go through ``gin_layer``."""
+    (0 or 1 / (1 - p)) or None.  d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes go through ``gin_layer``."""
 
     @staticmethod
     def forward(ctx, x, W1T, b1, W2T, b2, keep, pb):
@@ -1109,7 +1101,7 @@ class GinLayerFn(Function):
         N, d = x.shape
         if tuple(W1T.shape) != (d, d) or tuple(W2T.shape) != (d, d) or tuple(b1.shape) != (d,) or tuple(b2.shape) != (d,):
             raise ValueError("gin layer: weight shapes do not match x")
-        if not (gin_tile_ok(pb) and gin_layer_supported(d)):
+        if not (whole_tiles_ok(pb) and gin_layer_supported(d)):
             raise ValueError("gin layer: the fused kernels take d in {64, 128} on whole tiles; use gin_layer()")
         if keep is not None:
             require_rows(keep, "gin layer: keep", d)
@@ -1151,7 +1143,7 @@ def gin_layer(x, W1T, b1, W2T, b2, keep, pb, fused=True):
     bond types, no per-type bias and the self connection (W1, b1) under relu -- relu((sum_e agg_e + h) . W1T + b1) --, then the
     row linear with relu (with a dropout mask: identity, the mask, relu).  Both are differentiable through autograd."""
     d = x.shape[1]
-    if fused and x.is_cuda and gin_tile_ok(pb) and gin_layer_supported(d):
+    if fused and x.is_cuda and whole_tiles_ok(pb) and gin_layer_supported(d):
         return GinLayerFn.apply(x, W1T, b1, W2T, b2, keep, pb)
     GIN_PATHS["composed"] += 1
     t = MsgFn.apply(x, W1T.repeat(4, 1), torch.zeros(4, d, dtype=x.dtype, device=x.device), W1T, b1, pb, ACT["relu"])

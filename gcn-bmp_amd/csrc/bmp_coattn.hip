@@ -49,17 +49,6 @@ struct CoArgs {
     const float* gscale;                       // backward: device scalar dout1 / dout2 are multiplied with on load (null: 1)
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
-    return v;
-}
-
 // LDS carve-up shared by forward and backward; every extent scales with the launch's size class np
 struct CoLds {
     float* Cs;      // [np x ldc]
@@ -359,10 +348,10 @@ __global__ __launch_bounds__(NT) void k_coattn_fwd(CoArgs a) {
         const int n = wave == 0 ? n1 : n2;
         float mx = -INFINITY;
         for (int k = lane; k < n; k += 64) if (ww[k] > 0.f) mx = fmaxf(mx, sc[k]);
-        mx = wave_max(mx);
+        mx = bmp_wave_max(mx);
         float s = 0.f;
         for (int k = lane; k < n; k += 64) if (ww[k] > 0.f) s += ww[k] * bmp_exp(sc[k] - mx);
-        s = wave_sum(s);
+        s = bmp_wave_sum(s);
         float* alg = a.al1 == nullptr ? nullptr : (wave == 0 ? a.al1 + r1 : a.al2 + r2);
         for (int k = lane; k < n; k += 64) {
             const float al = ww[k] > 0.f ? bmp_exp(sc[k] - mx) / s : 0.f;
@@ -526,7 +515,7 @@ __global__ __launch_bounds__(NT) void k_coattn_bwd(CoArgs a) {
 #pragma unroll
             for (int q = 0; q < CO_DQ; ++q) {
                 const int row = rbase + NW * q;
-                const float dsum = wave_sum(dot[q]);
+                const float dsum = bmp_wave_sum(dot[q]);
                 if (lane == 0 && row < nrows) (row < n1 ? L.dots1 : L.dots2)[row < n1 ? row : row - n1] = dsum;
             }
         }
@@ -541,7 +530,7 @@ __global__ __launch_bounds__(NT) void k_coattn_bwd(CoArgs a) {
         const int n = wave == 0 ? n1 : n2;
         float tsum = 0.f;
         for (int k = lane; k < n; k += 64) tsum += al[k] * ww[k] * dt[k];
-        tsum = wave_sum(tsum);
+        tsum = bmp_wave_sum(tsum);
         for (int k = lane; k < n; k += 64) dt[k] = al[k] * (ww[k] * dt[k] - ww[k] * tsum);     // = ds_k
     }
     __syncthreads();
@@ -719,7 +708,7 @@ __global__ __launch_bounds__(NT) void k_coattn_bwd(CoArgs a) {
               for (int c = o + H + 1; c < ZC; ++c) dzr[c] = 0.f; }      // the row's padding columns: the same cache line
             mine += dv2;
         }
-        const float tot = wave_sum(mine);
+        const float tot = bmp_wave_sum(mine);
         if (lane == 0) L.dots1[wave] = tot;          // dots1 is dead by now; np >= 160 > NW
         __syncthreads();
         if (tid == 0) {
@@ -744,7 +733,7 @@ __global__ __launch_bounds__(NT) void k_coattn_bwd(CoArgs a) {
             { float* dzr = a.dZ2 + (size_t)(r2 + i) * ZC; dzr[o + H] = dv2;
               for (int c = o + H + 1; c < ZC; ++c) dzr[c] = 0.f; }      // the row's padding columns: the same cache line
         }
-        const float tot = wave_sum(dv2);
+        const float tot = bmp_wave_sum(dv2);
         if (lane == 0 && wave < 4) L.dots1[wave - 2] = tot;
     }
     __syncthreads();

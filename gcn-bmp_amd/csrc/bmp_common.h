@@ -67,6 +67,19 @@ __device__ __forceinline__ int bmp_acc_row(int reg, int lane) {
     return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
 }
 
+// Reductions over the 64 lanes of a wave: an xor butterfly, 32 down to 1; every lane ends with the result.
+template <typename T>
+__device__ __forceinline__ T bmp_wave_sum(T v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    return v;
+}
+__device__ __forceinline__ float bmp_wave_max(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+
 // Hardware transcendental forms (v_exp_f32 / v_rcp_f32, ~1e-7 absolute error on the outputs): three
 // instructions instead of the ~30 of ocml's expf/tanhf.  The gate nonlinearities run in the VALU shadow of
 // the MFMA phases and the co-attention softmaxes are chains of exps, so the libm forms were measurable;

@@ -13,56 +13,8 @@
 // h never leaves the CU between the gather and the second product.  The weight gradients dW2 = dp2^T t, dW1 = dp1^T s and the
 // bias gradients are the caller's two calls of bmp_linear_wgrad on the saved s, t and the dp2, dp1 written here.
 // Weights are K4-packed ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
-#include "bmp_kernels.h"
-
-#define GIN_T 128
-
-// acc[nb] += A(32 rows x K) . B(K x 32 cols per nb);  Ar = this lane's A row + 4 * (lane >> 5),
-// Bp = packed matrix + ((lane >> 5) * Nw + first column + (lane & 31)) * 4, column blocks 32 apart.
-template <int NB>
-__device__ __forceinline__ void gin_block_mma(f32x16 (&acc)[NB], const float* Ar, const float* __restrict__ Bp, int Nw, int K) {
-#pragma unroll 2
-    for (int k0 = 0; k0 < K; k0 += 8) {
-        const f32x4 a = *(const f32x4*)(Ar + k0);
-        f32x4 b[NB];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) b[nb] = *(const f32x4*)(Bp + ((size_t)(k0 >> 2) * Nw + nb * 32) * 4);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = bmp_mfma(a[t], b[nb][t], acc[nb]);
-    }
-}
-
-// one wave's product: acc = rows [32 b, 32 b + 32) of `opnd` times the columns of half `ch` of the packed D x D matrix Wp
-template <int D>
-__device__ __forceinline__ void gin_wave_mma(f32x16 (&acc)[D / 64], const float* opnd, const float* __restrict__ Wp, int b, int ch, int lane) {
-    constexpr int LD = D + 4, NB = D / 64;
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-    gin_block_mma<NB>(acc, opnd + (b * 32 + (lane & 31)) * LD + 4 * (lane >> 5),
-                      Wp + ((size_t)(lane >> 5) * D + ch * NB * 32 + (lane & 31)) * 4, D, D);
-}
-
-// tile-local gather of one row's quarter (4 threads per row): src[row] + sum over the row's entries of val * src[col - row0]
-template <int D>
-__device__ __forceinline__ void gin_tile_gather(f32x4 (&acc)[D / 16], const float* src, int row, int q, int row0,
-                                                const int* __restrict__ ptr, const int* __restrict__ col, const float* __restrict__ val) {
-    constexpr int LD = D + 4, F = D / 16;
-    const float* s0 = src + row * LD + q * (D / 4);
-#pragma unroll
-    for (int f = 0; f < F; ++f) acc[f] = *(const f32x4*)(s0 + 4 * f);
-    for (int e = ptr[row0 + row]; e < ptr[row0 + row + 1]; ++e) {
-        const int j = (col[e] >> 2) - row0;
-        if ((unsigned)j >= (unsigned)GIN_T) continue;          // (molecules never straddle a tile on this path: never taken)
-        const float v = val[e];
-        const float* s = src + j * LD + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) acc[f] += *(const f32x4*)(s + 4 * f) * v;
-    }
-}
+// The tile load, the MFMA loop, the wave product, the gather and the launch are the shared ones of bmp_wtile.h.
+#include "bmp_wtile.h"
 
 template <int D>
 __global__ __launch_bounds__(512) void k_gin_tile_fwd(const float* __restrict__ h, const int* __restrict__ ptr, const int* __restrict__ col,
@@ -73,49 +25,46 @@ __global__ __launch_bounds__(512) void k_gin_tile_fwd(const float* __restrict__ 
     constexpr int LD = D + 4, NB = D / 64, F = D / 16;
     extern __shared__ float sm[];
     float* ta = sm;
-    float* tb = sm + GIN_T * LD;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row0 = blockIdx.x * GIN_T;
-    for (int i = tid; i < GIN_T * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        *(f32x4*)(ta + r * LD + 4 * q4) = *(const f32x4*)(h + (size_t)(row0 + r) * D + 4 * q4);
-    }
+    float* tb = sm + WT_R * LD;
+    const int tid = threadIdx.x;
+    const WtWave wv = wt_wave(tid);
+    const int row0 = blockIdx.x * WT_R;
+    wt_load_tile<D>(ta, h, row0, tid);
     __syncthreads();
     {
         const int row = tid >> 2, q = tid & 3;
         f32x4 acc[F];
-        gin_tile_gather<D>(acc, ta, row, q, row0, ptr, col, val);
+        wt_tile_gather<D, false>(acc, ta, row, q, row0, ptr, col, val);
         float* d = tb + row * LD + q * (D / 4);
         float* gq = s + (size_t)(row0 + row) * D + q * (D / 4);
 #pragma unroll
         for (int f = 0; f < F; ++f) { *(f32x4*)(d + 4 * f) = acc[f]; *(f32x4*)(gq + 4 * f) = acc[f]; }
     }
     __syncthreads();
-    const int b = w >> 1, ch = w & 1;
     f32x16 acc[NB];
-    gin_wave_mma<D>(acc, tb, W1p, b, ch, lane);
+    wt_wave_mma<D>(acc, tb, LD, W1p, D, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
         const float bc = b1[c];
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const float v = acc[nb][reg] + bc;
-            ta[(b * 32 + bmp_acc_row(reg, lane)) * LD + c] = v > 0.f ? v : 0.f;
+            ta[wt_row(wv, reg) * LD + c] = v > 0.f ? v : 0.f;
         }
     }
     __syncthreads();
-    gin_wave_mma<D>(acc, ta, W2p, b, ch, lane);
+    wt_wave_mma<D>(acc, ta, LD, W2p, D, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
         const float bc = b2[c];
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) tb[(b * 32 + bmp_acc_row(reg, lane)) * LD + c] = acc[nb][reg] + bc;
+        for (int reg = 0; reg < 16; ++reg) tb[wt_row(wv, reg) * LD + c] = acc[nb][reg] + bc;
     }
     __syncthreads();
     const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < GIN_T * (D / 4); i += 512) {
+    for (int i = tid; i < WT_R * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);
         const size_t g = (size_t)(row0 + r) * D + 4 * q4;
         *(f32x4*)(t + g) = *(const f32x4*)(ta + r * LD + 4 * q4);
@@ -135,10 +84,11 @@ __global__ __launch_bounds__(512) void k_gin_tile_bwd(const float* __restrict__ 
     constexpr int LD = D + 4, NB = D / 64, F = D / 16;
     extern __shared__ float sm[];
     float* ta = sm;
-    float* tb = sm + GIN_T * LD;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row0 = blockIdx.x * GIN_T;
-    for (int i = tid; i < GIN_T * (D / 4); i += 512) {
+    float* tb = sm + WT_R * LD;
+    const int tid = threadIdx.x;
+    const WtWave wv = wt_wave(tid);
+    const int row0 = blockIdx.x * WT_R;
+    for (int i = tid; i < WT_R * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);
         const size_t g = (size_t)(row0 + r) * D + 4 * q4;
         const f32x4 ov = *(const f32x4*)(out + g);
@@ -151,25 +101,24 @@ __global__ __launch_bounds__(512) void k_gin_tile_bwd(const float* __restrict__ 
         *(f32x4*)(tb + r * LD + 4 * q4) = *(const f32x4*)(t + g);
     }
     __syncthreads();
-    const int b = w >> 1, ch = w & 1;
     f32x16 acc[NB];
-    gin_wave_mma<D>(acc, ta, W2np, b, ch, lane);
+    wt_wave_mma<D>(acc, ta, LD, W2np, D, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {             // every (row, column) of B belongs to one lane: in place
-            float* p = tb + (b * 32 + bmp_acc_row(reg, lane)) * LD + c;
+            float* p = tb + wt_row(wv, reg) * LD + c;
             *p = *p > 0.f ? acc[nb][reg] : 0.f;
         }
     }
     __syncthreads();
-    gin_wave_mma<D>(acc, tb, W1np, b, ch, lane);
+    wt_wave_mma<D>(acc, tb, LD, W1np, D, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) ta[(b * 32 + bmp_acc_row(reg, lane)) * LD + c] = acc[nb][reg];
+        for (int reg = 0; reg < 16; ++reg) ta[wt_row(wv, reg) * LD + c] = acc[nb][reg];
     }
     __syncthreads();
     {
@@ -179,7 +128,7 @@ __global__ __launch_bounds__(512) void k_gin_tile_bwd(const float* __restrict__ 
 #pragma unroll
         for (int f = 0; f < F; ++f) *(f32x4*)(g1 + 4 * f) = *(const f32x4*)(pq + 4 * f);
         f32x4 a[F];
-        gin_tile_gather<D>(a, ta, row, q, row0, ptrT, colT, valT);
+        wt_tile_gather<D, false>(a, ta, row, q, row0, ptrT, colT, valT);
         float* gq = dh + (size_t)(row0 + row) * D + q * (D / 4);
 #pragma unroll
         for (int f = 0; f < F; ++f) *(f32x4*)(gq + 4 * f) = a[f];
@@ -187,7 +136,6 @@ __global__ __launch_bounds__(512) void k_gin_tile_bwd(const float* __restrict__ 
 }
 
 extern "C" int bmp_gin_layer_supported(int d) { return d == 64 || d == 128; }
-static size_t gin_tile_lds(int d) { return (size_t)2 * GIN_T * (d + 4) * sizeof(float); }
 
 // W1p / W2p [d x d]: W1^T / W2^T (K-major) K4-packed.  keep [N x d] or null (no dropout).  Saves s, t [N x d]; N = 128 n_tiles.
 extern "C" int bmp_gin_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
@@ -195,11 +143,7 @@ extern "C" int bmp_gin_layer_tile_fwd(const float* h, int n_tiles, int d, const 
                                       float* s, float* t, float* out, hipStream_t st) {
     BMP_REQUIRE(h && n_tiles > 0 && bmp_gin_layer_supported(d) && csr_ptr && W1p && b1 && W2p && b2 && s && t && out);
     BMP_REQUIRE((((uintptr_t)h | (uintptr_t)W1p | (uintptr_t)W2p | (uintptr_t)keep | (uintptr_t)s | (uintptr_t)t | (uintptr_t)out) & 15) == 0);
-    const void* fn = d == 128 ? (const void*)k_gin_tile_fwd<128> : (const void*)k_gin_tile_fwd<64>;
-    if (int rc = bmp_lds_attr(fn, gin_tile_lds(d))) return rc;
-    if (d == 128) hipLaunchKernelGGL(k_gin_tile_fwd<128>, dim3(n_tiles), dim3(512), gin_tile_lds(d), st, h, csr_ptr, csr_col, csr_val, W1p, b1, W2p, b2, keep, s, t, out);
-    else hipLaunchKernelGGL(k_gin_tile_fwd<64>, dim3(n_tiles), dim3(512), gin_tile_lds(d), st, h, csr_ptr, csr_col, csr_val, W1p, b1, W2p, b2, keep, s, t, out);
-    BMP_LAUNCH_CHECK();
+    WT_LAUNCH(k_gin_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, W1p, b1, W2p, b2, keep, s, t, out);
     return 0;
 }
 // W2np / W1np [d x d]: W2 / W1 in the reference layout [out x in] (the K-major operands of dt = dp2 . W2, ds = dp1 . W1), K4-packed.
@@ -209,10 +153,6 @@ extern "C" int bmp_gin_layer_tile_bwd(const float* dout, const float* out, const
     BMP_REQUIRE(dout && out && t && n_tiles > 0 && bmp_gin_layer_supported(d) && csrT_ptr && W2np && W1np && dp2 && dp1 && dh);
     BMP_REQUIRE((((uintptr_t)dout | (uintptr_t)out | (uintptr_t)keep | (uintptr_t)t | (uintptr_t)W2np | (uintptr_t)W1np | (uintptr_t)dp2 |
                   (uintptr_t)dp1 | (uintptr_t)dh) & 15) == 0);
-    const void* fn = d == 128 ? (const void*)k_gin_tile_bwd<128> : (const void*)k_gin_tile_bwd<64>;
-    if (int rc = bmp_lds_attr(fn, gin_tile_lds(d))) return rc;
-    if (d == 128) hipLaunchKernelGGL(k_gin_tile_bwd<128>, dim3(n_tiles), dim3(512), gin_tile_lds(d), st, dout, out, keep, t, csrT_ptr, csrT_col, csrT_val, W2np, W1np, dp2, dp1, dh);
-    else hipLaunchKernelGGL(k_gin_tile_bwd<64>, dim3(n_tiles), dim3(512), gin_tile_lds(d), st, dout, out, keep, t, csrT_ptr, csrT_col, csrT_val, W2np, W1np, dp2, dp1, dh);
-    BMP_LAUNCH_CHECK();
+    WT_LAUNCH(k_gin_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dout, out, keep, t, csrT_ptr, csrT_col, csrT_val, W2np, W1np, dp2, dp1, dh);
     return 0;
 }

@@ -212,67 +212,85 @@ extern "C" int bmp_embed_bwd(const int* ids, const float* dout, int N, int d, in
 //   pass 1: per 256-row block and type, the number of such rows;  pass 2: every block sums the counts of the blocks in
 //   front of it (at most N / 256 of them) and writes its rows at their ranks.  Fixed order, no atomics.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int tr_mask(const int* __restrict__ ptr, const int* __restrict__ col, const int* __restrict__ row_mol,
-                                       int row, int N) {
+// The source of a row's membership mask (bit l: the row is on list l): a CSR -- bit e for an entry of bond type e, bit 4
+// for a row of a molecule when row_mol is given -- or, CLS, a class array: class k in 1..NL gives bit k - 1, class 0 none.
+template <int NL, bool CLS>
+__device__ __forceinline__ int row_lists_mask(const RowListSrc& s, int row, int N) {
     int m = 0;
     if (row < N) {
-        for (int e = ptr[row]; e < ptr[row + 1]; ++e) m |= 1 << (col[e] & 3);
-        if (row_mol && row_mol[row] >= 0) m |= 16;          // list 4: the rows of a molecule (real atoms and pad rows)
+        if constexpr (CLS) {
+            const int k = s.cls[row];
+            m = (k >= 1 && k <= NL) ? 1 << (k - 1) : 0;
+        } else {
+            for (int e = s.ptr[row]; e < s.ptr[row + 1]; ++e) m |= 1 << (s.col[e] & 3);
+            if (s.row_mol && s.row_mol[row] >= 0) m |= 16;          // list 4: the rows of a molecule (real atoms and pad rows)
+        }
     }
     return m;
 }
-template <int NE>
-__global__ __launch_bounds__(256) void k_type_rows_count(const int* __restrict__ ptr, const int* __restrict__ col,
-                                                         const int* __restrict__ row_mol, int N, int* __restrict__ bcnt) {
-    __shared__ int wc[4][NE];
+template <int NL, bool CLS>
+__global__ __launch_bounds__(256) void k_row_lists_count(RowListSrc src, int N, int* __restrict__ bcnt) {
+    __shared__ int wc[4][NL];
     const int row = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int m = tr_mask(ptr, col, row_mol, row, N);
+    const int m = row_lists_mask<NL, CLS>(src, row, N);
 #pragma unroll
-    for (int e = 0; e < NE; ++e) {
+    for (int e = 0; e < NL; ++e) {
         const int c = __popcll(__ballot((m >> e) & 1));
         if (lane == 0) wc[w][e] = c;
     }
     __syncthreads();
-    if (threadIdx.x < NE) bcnt[blockIdx.x * NE + threadIdx.x] = wc[0][threadIdx.x] + wc[1][threadIdx.x] + wc[2][threadIdx.x] + wc[3][threadIdx.x];
+    if (threadIdx.x < NL) bcnt[blockIdx.x * NL + threadIdx.x] = wc[0][threadIdx.x] + wc[1][threadIdx.x] + wc[2][threadIdx.x] + wc[3][threadIdx.x];
 }
-template <int NE>
-__global__ __launch_bounds__(256) void k_type_rows_emit(const int* __restrict__ ptr, const int* __restrict__ col,
-                                                        const int* __restrict__ row_mol, int N, const int* __restrict__ bcnt,
-                                                        int* __restrict__ idx, int* __restrict__ cnt) {
-    __shared__ int base[NE], wc[4][NE], red[4][NE];
+template <int NL, bool CLS>
+__global__ __launch_bounds__(256) void k_row_lists_emit(RowListSrc src, int N, const int* __restrict__ bcnt, int* __restrict__ idx,
+                                                        int* __restrict__ cnt) {
+    __shared__ int base[NL], wc[4][NL], red[4][NL];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int row = blockIdx.x * 256 + tid;
     // offsets of this block: the counts of the blocks in front of it, summed in a fixed order
-    int part[NE];
+    int part[NL];
 #pragma unroll
-    for (int e = 0; e < NE; ++e) part[e] = 0;
+    for (int e = 0; e < NL; ++e) part[e] = 0;
     for (int b = tid; b < (int)blockIdx.x; b += 256)
 #pragma unroll
-        for (int e = 0; e < NE; ++e) part[e] += bcnt[b * NE + e];
+        for (int e = 0; e < NL; ++e) part[e] += bcnt[b * NL + e];
 #pragma unroll
-    for (int e = 0; e < NE; ++e) {
-        int v = part[e];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+    for (int e = 0; e < NL; ++e) {
+        const int v = bmp_wave_sum(part[e]);
         if (lane == 0) red[w][e] = v;
     }
-    const int m = tr_mask(ptr, col, row_mol, row, N);
-    unsigned long long bal[NE];
+    const int m = row_lists_mask<NL, CLS>(src, row, N);
+    unsigned long long bal[NL];
 #pragma unroll
-    for (int e = 0; e < NE; ++e) {
+    for (int e = 0; e < NL; ++e) {
         bal[e] = __ballot((m >> e) & 1);
         if (lane == 0) wc[w][e] = __popcll(bal[e]);
     }
     __syncthreads();
-    if (tid < NE) base[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    if (tid < NL) base[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
     __syncthreads();
 #pragma unroll
-    for (int e = 0; e < NE; ++e) {
+    for (int e = 0; e < NL; ++e) {
         int off = base[e];
         for (int q = 0; q < w; ++q) off += wc[q][e];
         if ((m >> e) & 1) idx[(size_t)e * N + off + __popcll(bal[e] & ((1ull << lane) - 1ull))] = row;
     }
-    if (blockIdx.x == gridDim.x - 1 && tid < NE) cnt[tid] = base[tid] + wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
+    if (blockIdx.x == gridDim.x - 1 && tid < NL) cnt[tid] = base[tid] + wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
+}
+
+template <int NL, bool CLS>
+static int row_lists_launch(const RowListSrc& src, int N, int* idx, int* cnt, int* ws, hipStream_t st) {
+    const int nb = (N + 255) / 256;
+    hipLaunchKernelGGL((k_row_lists_count<NL, CLS>), dim3(nb), dim3(256), 0, st, src, N, ws);
+    BMP_LAUNCH_CHECK();
+    hipLaunchKernelGGL((k_row_lists_emit<NL, CLS>), dim3(nb), dim3(256), 0, st, src, N, (const int*)ws, idx, cnt);
+    BMP_LAUNCH_CHECK();
+    return 0;
+}
+int bmp_launch_row_lists(const RowListSrc& src, int n_lists, int N, int* idx, int* cnt, int* ws, hipStream_t st) {
+    if (src.cls) return n_lists == 7 ? row_lists_launch<7, true>(src, N, idx, cnt, ws, st) : -1;
+    if (n_lists == 4) return row_lists_launch<4, false>(src, N, idx, cnt, ws, st);
+    return n_lists == 5 ? row_lists_launch<5, false>(src, N, idx, cnt, ws, st) : -1;
 }
 
 // idx [4 x N] int32, cnt [4] int32; ws: bmp_type_rows_ws_ints(N) ints.  ptr / col: the CSR whose gather the lists describe (the
@@ -280,12 +298,7 @@ __global__ __launch_bounds__(256) void k_type_rows_emit(const int* __restrict__ 
 extern "C" size_t bmp_type_rows_ws_ints(int N) { return (size_t)((N + 255) / 256) * 8; }
 extern "C" int bmp_type_rows(const int* csr_ptr, const int* csr_col, int N, int* idx, int* cnt, int* ws, hipStream_t st) {
     BMP_REQUIRE(csr_ptr && N > 0 && idx && cnt && ws);          // (csr_col may be NULL: a batch without a single bond)
-    const int nb = (N + 255) / 256;
-    hipLaunchKernelGGL(k_type_rows_count<4>, dim3(nb), dim3(256), 0, st, csr_ptr, csr_col, (const int*)nullptr, N, ws);
-    BMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_type_rows_emit<4>, dim3(nb), dim3(256), 0, st, csr_ptr, csr_col, (const int*)nullptr, N, ws, idx, cnt);
-    BMP_LAUNCH_CHECK();
-    return 0;
+    return bmp_launch_row_lists(RowListSrc{csr_ptr, csr_col, nullptr, nullptr}, 4, N, idx, cnt, ws, st);
 }
 // The same with a FIFTH list: the rows that belong to a molecule (row_mol >= 0: real atoms and pad rows), ascending -- idx
 // [5 x N], cnt [5].  For a batch whose tiles sit at a fixed stride (one molecule per tile: three rows of four belong to no
@@ -293,10 +306,5 @@ extern "C" int bmp_type_rows(const int* csr_ptr, const int* csr_col, int N, int*
 extern "C" int bmp_type_rows_live(const int* csr_ptr, const int* csr_col, const int* row_mol, int N, int* idx, int* cnt, int* ws,
                                   hipStream_t st) {
     BMP_REQUIRE(csr_ptr && row_mol && N > 0 && idx && cnt && ws);
-    const int nb = (N + 255) / 256;
-    hipLaunchKernelGGL(k_type_rows_count<5>, dim3(nb), dim3(256), 0, st, csr_ptr, csr_col, row_mol, N, ws);
-    BMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_type_rows_emit<5>, dim3(nb), dim3(256), 0, st, csr_ptr, csr_col, row_mol, N, ws, idx, cnt);
-    BMP_LAUNCH_CHECK();
-    return 0;
+    return bmp_launch_row_lists(RowListSrc{csr_ptr, csr_col, row_mol, nullptr}, 5, N, idx, cnt, ws, st);
 }

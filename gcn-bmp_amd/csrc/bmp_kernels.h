@@ -110,6 +110,13 @@ int bmp_launch_gather_fwd(const float* x, int ldx, int N, int d, const int* ptr,
 int bmp_launch_gather_bwd(const float* dagg, int N, int d, const int* ptrT, const int* colT, const float* valT,
                           float* dx, int lddx, int accumulate, hipStream_t st);
 
+// Ascending row lists, built in two passes with no atomics: idx[l * N + p] = the p-th row on list l, cnt[l] = their number;
+// ws: (N + 255) / 256 * n_lists ints.  A row's lists come from a CSR -- n_lists = 4: list e = the rows with an entry of bond
+// type e (col & 3); 5: and, with row_mol, list 4 = the rows of a molecule -- or from a class array -- cls given, n_lists = 7:
+// list k - 1 = the rows of class k, class 0 on none.
+struct RowListSrc { const int* ptr; const int* col; const int* row_mol; const int* cls; };
+int bmp_launch_row_lists(const RowListSrc& src, int n_lists, int N, int* idx, int* cnt, int* ws, hipStream_t st);
+
 // ---------------------------------------------------------------------------------------------
 // Layer aggregators (bmp_agg.hip): bmp_layer_agg_fwd / _bwd / _ws_floats of include/bmp.h
 // ---------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@
 // The weight gradient of the widths the listed MFMA launch takes (64 <= d <= 128) runs as seven listed problems of
 // bmp_launch_wgrad_fused over the class row lists; the other widths take k_nfp_wgrad below.
 #include <string.h>
-#include "bmp_kernels.h"
+#include "bmp_wtile.h"
 
 #define NFP_NCLS 7          // degree classes 1..7 (max_degree 6 + 1, nfp.py:26,111); class 0 = none of them
 #define NFP_RB 8            // rows per workgroup of the row-wise kernels (N is a multiple of 128)
@@ -50,69 +50,12 @@ extern "C" int bmp_nfp_rows(const int* csrT_ptr, const float* csrT_val, const in
 
 // ---------------------------------------------------------------------------------------------
 // rows by degree class: idx[(k - 1) * N + p] = the p-th row (ascending) of class k, cnt[k - 1] = their number.  Two passes
-// as bmp_type_rows: per 256-row block the count per class, then every block ranks its rows behind the blocks in front of it.
+// as bmp_type_rows: the row-list builder of bmp_graph.hip with the class array as the source of a row's membership.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_nfp_deg_count(const int* __restrict__ cls, int N, int* __restrict__ bcnt) {
-    __shared__ int wc[4][NFP_NCLS];
-    const int row = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int k = row < N ? cls[row] : 0;
-#pragma unroll
-    for (int c = 0; c < NFP_NCLS; ++c) {
-        const int n = __popcll(__ballot(k == c + 1));
-        if (lane == 0) wc[w][c] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x < NFP_NCLS) {
-        const int c = threadIdx.x;
-        bcnt[blockIdx.x * 8 + c] = wc[0][c] + wc[1][c] + wc[2][c] + wc[3][c];
-    }
-}
-__global__ __launch_bounds__(256) void k_nfp_deg_emit(const int* __restrict__ cls, int N, const int* __restrict__ bcnt,
-                                                      int* __restrict__ idx, int* __restrict__ cnt) {
-    __shared__ int base[NFP_NCLS], wc[4][NFP_NCLS], red[4][NFP_NCLS];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row = blockIdx.x * 256 + tid;
-    int part[NFP_NCLS];
-#pragma unroll
-    for (int c = 0; c < NFP_NCLS; ++c) part[c] = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256)
-#pragma unroll
-        for (int c = 0; c < NFP_NCLS; ++c) part[c] += bcnt[b * 8 + c];
-#pragma unroll
-    for (int c = 0; c < NFP_NCLS; ++c) {
-        int v = part[c];
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-        if (lane == 0) red[w][c] = v;
-    }
-    const int k = row < N ? cls[row] : 0;
-    int rank = 0;
-#pragma unroll
-    for (int c = 0; c < NFP_NCLS; ++c) {
-        const unsigned long long bal = __ballot(k == c + 1);
-        if (lane == 0) wc[w][c] = __popcll(bal);
-        if (k == c + 1) rank = __popcll(bal & ((1ull << lane) - 1ull));
-    }
-    __syncthreads();
-    if (tid < NFP_NCLS) base[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-    __syncthreads();
-    if (k > 0) {
-        int off = base[k - 1];
-        for (int q = 0; q < w; ++q) off += wc[q][k - 1];
-        idx[(size_t)(k - 1) * N + off + rank] = row;
-    }
-    if (blockIdx.x == gridDim.x - 1 && tid < NFP_NCLS) cnt[tid] = base[tid] + wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
-}
-
 extern "C" size_t bmp_nfp_deg_rows_ws_ints(int N) { return (size_t)((N + 255) / 256) * 8; }
 extern "C" int bmp_nfp_deg_rows(const int* deg_class, int N, int* idx, int* cnt, int* ws, hipStream_t st) {
     BMP_REQUIRE(deg_class && N > 0 && idx && cnt && ws);
-    const int nb = (N + 255) / 256;
-    hipLaunchKernelGGL(k_nfp_deg_count, dim3(nb), dim3(256), 0, st, deg_class, N, ws);
-    BMP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_nfp_deg_emit, dim3(nb), dim3(256), 0, st, deg_class, N, (const int*)ws, idx, cnt);
-    BMP_LAUNCH_CHECK();
-    return 0;
+    return bmp_launch_row_lists(RowListSrc{nullptr, nullptr, nullptr, deg_class}, NFP_NCLS, N, idx, cnt, ws, st);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -372,16 +315,6 @@ extern "C" int bmp_nfp_layer_wgrad(const float* fv, const float* dpre, int N, in
 // workgroup; one wave per row for the softmax).  k_nfp_readout_sum: g[mol, :] (=|+=) sum over the molecule's rows, in row
 // order, of row_w * s[row, :].
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float nfp_wave_max(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = fmaxf(v, __shfl_xor(v, s));
-    return v;
-}
-__device__ __forceinline__ float nfp_wave_sum(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
 __global__ __launch_bounds__(128) void k_nfp_readout_rows(const float* __restrict__ h, int d, int o, const float* __restrict__ WT,
                                                           const float* __restrict__ b, float* __restrict__ sout) {
     extern __shared__ float sm[];                  // hs [NFP_RB][d] | zs [NFP_RB][o]
@@ -408,10 +341,10 @@ __global__ __launch_bounds__(128) void k_nfp_readout_rows(const float* __restric
     for (int r = w; r < NFP_RB; r += nw) {
         float mx = -3.0e38f;
         for (int c = lane; c < o; c += 64) mx = fmaxf(mx, zs[r * o + c]);
-        mx = nfp_wave_max(mx);
+        mx = bmp_wave_max(mx);
         float sum = 0.f;
         for (int c = lane; c < o; c += 64) { const float e = bmp_exp(zs[r * o + c] - mx); zs[r * o + c] = e; sum += e; }
-        sum = nfp_wave_sum(sum);
+        sum = bmp_wave_sum(sum);
         const float inv = 1.0f / sum;
         for (int c = lane; c < o; c += 64) sout[(size_t)(row0 + r) * o + c] = zs[r * o + c] * inv;
     }
@@ -459,7 +392,7 @@ __global__ __launch_bounds__(128) void k_nfp_readout_bwd(const float* __restrict
         float dot = 0.f;
         if (rw != 0.f)
             for (int c = lane; c < o; c += 64) dot = fmaf(dg[(size_t)m * o + c], s[(size_t)row * o + c], dot);
-        dot = nfp_wave_sum(dot);
+        dot = bmp_wave_sum(dot);
         for (int c = lane; c < o; c += 64) {
             const float v = rw != 0.f ? rw * s[(size_t)row * o + c] * (dg[(size_t)m * o + c] - dot) : 0.f;
             sm[r * o + c] = v;
@@ -513,39 +446,20 @@ extern "C" int bmp_nfp_readout_bwd(const float* dg, const float* h, const float*
 // accumulators receive its product once plus exact zeros; blocks of class-0 rows (pad rows, dead rows at the tile's end,
 // hubs) run no MFMA at all.  Work = (block, class) pairs present: at most blocks + classes - 1 block passes per tile.
 // Weights are K4-packed per class ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
+// The tile load, the MFMA loop, the wave product, the gather and the launch are the shared ones of bmp_wtile.h.
 // =============================================================================================
-#define NFP_T 128
 #define NFP_LDZ 132         // row stride of the readout's z / dz tile (o <= 128)
 
-// acc[nb] += A(32 ranked rows, rows of other classes zeroed) . B(K x 32 cols per nb);  Ar = this lane's A row + 4 * (lane >> 5),
-// Bp = packed matrix + ((lane >> 5) * Nw + first column + (lane & 31)) * 4, column blocks 32 apart.
-template <int NB>
-__device__ __forceinline__ void nfp_block_mma(f32x16 (&acc)[NB], const float* Ar, bool mine, const float* __restrict__ Bp, int Nw, int K) {
-    const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll 2
-    for (int k0 = 0; k0 < K; k0 += 8) {
-        f32x4 a = *(const f32x4*)(Ar + k0);
-        a = mine ? a : z4;
-        f32x4 b[NB];
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) b[nb] = *(const f32x4*)(Bp + ((size_t)(k0 >> 2) * Nw + nb * 32) * 4);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) acc[nb] = bmp_mfma(a[t], b[nb][t], acc[nb]);
-    }
-}
-
-struct NfpOrder { int scl[NFP_T]; int skey[NFP_T]; unsigned char inv[NFP_T]; unsigned char perm[NFP_T]; };
+struct NfpOrder { int scl[WT_R]; int skey[WT_R]; unsigned char inv[WT_R]; unsigned char perm[WT_R]; };
 // rank of every tile row in the order (class 1..7, class 0; row); ends with a workgroup barrier
 __device__ __forceinline__ void nfp_rank_rows(NfpOrder& o, const int* __restrict__ cls, int row0) {
     const int tid = threadIdx.x;
-    if (tid < NFP_T) o.scl[tid] = cls[row0 + tid];
+    if (tid < WT_R) o.scl[tid] = cls[row0 + tid];
     __syncthreads();
-    if (tid < NFP_T) {
+    if (tid < WT_R) {
         const int c = o.scl[tid], key = c ? c : 8;
         int pos = 0;
-        for (int j = 0; j < NFP_T; ++j) {
+        for (int j = 0; j < WT_R; ++j) {
             const int cj = o.scl[j], kj = cj ? cj : 8;
             pos += (kj < key || (kj == key && j < tid)) ? 1 : 0;
         }
@@ -555,33 +469,14 @@ __device__ __forceinline__ void nfp_rank_rows(NfpOrder& o, const int* __restrict
     }
     __syncthreads();
 }
-// the class walk of one wave: acc = ranked block b of `opnd` times the class matrices Wp [7][D x D packed]
+// the class walk of one wave: acc = ranked block wv.b of `opnd` times the class matrices Wp [7][D x D packed]
 template <int D>
 __device__ __forceinline__ void nfp_class_walk(f32x16 (&acc)[D / 64], const float* opnd, const NfpOrder& o, const float* __restrict__ Wp,
-                                               int b, int ch, int lane) {
-    constexpr int LD = D + 4, NB = D / 64;
-    const int c_l = o.skey[b * 32 + (lane & 31)];
-    const float* Ar = opnd + (b * 32 + (lane & 31)) * LD + 4 * (lane >> 5);
-    const size_t boff = ((size_t)(lane >> 5) * D + ch * NB * 32 + (lane & 31)) * 4;
+                                               WtWave wv) {
+    const int c_l = o.skey[wv.b * 32 + (wv.lane & 31)];
+    const WtLane p = wt_wave_open<D>(acc, opnd, D + 4, wv);
     for (int k = 1; k <= NFP_NCLS; ++k)
-        if (__ballot(c_l == k)) nfp_block_mma<NB>(acc, Ar, c_l == k, Wp + (size_t)(k - 1) * D * D + boff, D, D);
-}
-// tile-local gather of one row's quarter (4 threads per row): self * src[row] + sum over the row's entries of val * src[col - row0]
-template <int D>
-__device__ __forceinline__ void nfp_tile_gather(f32x4 (&acc)[D / 16], const float* src, int row, int q, int row0, float self,
-                                                const int* __restrict__ ptr, const int* __restrict__ col, const float* __restrict__ val) {
-    constexpr int LD = D + 4, F = D / 16;
-    const float* s0 = src + row * LD + q * (D / 4);
-#pragma unroll
-    for (int f = 0; f < F; ++f) acc[f] = *(const f32x4*)(s0 + 4 * f) * self;
-    for (int e = ptr[row0 + row]; e < ptr[row0 + row + 1]; ++e) {
-        const int j = (col[e] >> 2) - row0;
-        if ((unsigned)j >= (unsigned)NFP_T) continue;          // (molecules never straddle a tile: never taken)
-        const float v = val[e];
-        const float* s = src + j * LD + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) acc[f] += *(const f32x4*)(s + 4 * f) * v;
-    }
+        if (__ballot(c_l == k)) wt_block_mma<D / 64, true>(acc, p.Ar, Wp + (size_t)(k - 1) * D * D + p.boff, D, D, c_l == k);
 }
 
 template <int D>
@@ -592,39 +487,32 @@ __global__ __launch_bounds__(512) void k_nfp_tile_fwd(const float* __restrict__ 
     constexpr int LD = D + 4, NB = D / 64, F = D / 16;
     extern __shared__ float sm[];
     float* ht = sm;                        // h tile, tile-row order
-    float* ft = sm + NFP_T * LD;           // fv tile, ranked order
+    float* ft = sm + WT_R * LD;            // fv tile, ranked order
     __shared__ NfpOrder o;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row0 = blockIdx.x * NFP_T;
-    for (int i = tid; i < NFP_T * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        *(f32x4*)(ht + r * LD + 4 * q4) = *(const f32x4*)(h + (size_t)(row0 + r) * D + 4 * q4);
-    }
+    const int tid = threadIdx.x;
+    const WtWave wv = wt_wave(tid);
+    const int row0 = blockIdx.x * WT_R;
+    wt_load_tile<D>(ht, h, row0, tid);
     nfp_rank_rows(o, cls, row0);           // (its barriers also publish the h tile)
     {
         const int row = tid >> 2, q = tid & 3;
         f32x4 acc[F];
-        nfp_tile_gather<D>(acc, ht, row, q, row0, self_w[row0 + row], ptr, col, val);
+        wt_tile_gather<D, true>(acc, ht, row, q, row0, ptr, col, val, self_w[row0 + row]);
         float* d = ft + o.inv[row] * LD + q * (D / 4);
         float* gq = fv + (size_t)(row0 + row) * D + q * (D / 4);
 #pragma unroll
         for (int f = 0; f < F; ++f) { *(f32x4*)(d + 4 * f) = acc[f]; *(f32x4*)(gq + 4 * f) = acc[f]; }
     }
     __syncthreads();
-    const int b = w >> 1, ch = w & 1;
     f32x16 acc[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-    nfp_class_walk<D>(acc, ft, o, WTp, b, ch, lane);
+    nfp_class_walk<D>(acc, ft, o, WTp, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
         const float bc = B[c];
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-            const int row = o.perm[b * 32 + bmp_acc_row(reg, lane)];
+            const int row = o.perm[wt_row(wv, reg)];
             out[(size_t)(row0 + row) * D + c] = bmp_sigmoid(acc[nb][reg] + bc);
         }
     }
@@ -639,12 +527,13 @@ __global__ __launch_bounds__(512) void k_nfp_tile_bwd(const float* __restrict__ 
     constexpr int LD = D + 4, NB = D / 64, F = D / 16;
     extern __shared__ float sm[];
     float* dt = sm;                        // dpre tile, ranked order
-    float* gt = sm + NFP_T * LD;           // dfv tile, tile-row order
+    float* gt = sm + WT_R * LD;            // dfv tile, tile-row order
     __shared__ NfpOrder o;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row0 = blockIdx.x * NFP_T;
+    const int tid = threadIdx.x;
+    const WtWave wv = wt_wave(tid);
+    const int row0 = blockIdx.x * WT_R;
     nfp_rank_rows(o, cls, row0);
-    for (int i = tid; i < NFP_T * (D / 4); i += 512) {
+    for (int i = tid; i < WT_R * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);
         const size_t g = (size_t)(row0 + r) * D + 4 * q4;
         const f32x4 ov = *(const f32x4*)(out + g), gv = *(const f32x4*)(dout + g);
@@ -654,24 +543,19 @@ __global__ __launch_bounds__(512) void k_nfp_tile_bwd(const float* __restrict__ 
         *(f32x4*)(dt + o.inv[r] * LD + 4 * q4) = v;
     }
     __syncthreads();
-    const int b = w >> 1, ch = w & 1;
     f32x16 acc[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-    nfp_class_walk<D>(acc, dt, o, Wnp, b, ch, lane);
+    nfp_class_walk<D>(acc, dt, o, Wnp, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) gt[o.perm[b * 32 + bmp_acc_row(reg, lane)] * LD + c] = acc[nb][reg];
+        for (int reg = 0; reg < 16; ++reg) gt[o.perm[wt_row(wv, reg)] * LD + c] = acc[nb][reg];
     }
     __syncthreads();
     {
         const int row = tid >> 2, q = tid & 3;
         f32x4 a[F];
-        nfp_tile_gather<D>(a, gt, row, q, row0, self_w[row0 + row], ptrT, colT, valT);
+        wt_tile_gather<D, true>(a, gt, row, q, row0, ptrT, colT, valT, self_w[row0 + row]);
         float* gq = dh + (size_t)(row0 + row) * D + q * (D / 4);
 #pragma unroll
         for (int f = 0; f < F; ++f) *(f32x4*)(gq + 4 * f) = a[f];
@@ -679,7 +563,6 @@ __global__ __launch_bounds__(512) void k_nfp_tile_bwd(const float* __restrict__ 
 }
 
 extern "C" int bmp_nfp_layer_supported(int d) { return d == 64 || d == 128; }
-static size_t nfp_tile_lds(int d) { return (size_t)2 * NFP_T * (d + 4) * sizeof(float); }
 
 // The fused layer: d_in == d_out == d with bmp_nfp_layer_supported(d).  WTp [7][d x d]: W_k^T (K-major) K4-packed per class.
 extern "C" int bmp_nfp_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
@@ -687,11 +570,7 @@ extern "C" int bmp_nfp_layer_tile_fwd(const float* h, int n_tiles, int d, const 
                                       float* out, hipStream_t st) {
     BMP_REQUIRE(h && n_tiles > 0 && bmp_nfp_layer_supported(d) && csr_ptr && self_w && deg_class && WTp && B && fv && out);
     BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WTp | (uintptr_t)fv) & 15) == 0);
-    const void* fn = d == 128 ? (const void*)k_nfp_tile_fwd<128> : (const void*)k_nfp_tile_fwd<64>;
-    if (int rc = bmp_lds_attr(fn, nfp_tile_lds(d))) return rc;
-    if (d == 128) hipLaunchKernelGGL(k_nfp_tile_fwd<128>, dim3(n_tiles), dim3(512), nfp_tile_lds(d), st, h, csr_ptr, csr_col, csr_val, self_w, deg_class, WTp, B, fv, out);
-    else hipLaunchKernelGGL(k_nfp_tile_fwd<64>, dim3(n_tiles), dim3(512), nfp_tile_lds(d), st, h, csr_ptr, csr_col, csr_val, self_w, deg_class, WTp, B, fv, out);
-    BMP_LAUNCH_CHECK();
+    WT_LAUNCH(k_nfp_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, self_w, deg_class, WTp, B, fv, out);
     return 0;
 }
 // Wnp [7][d x d]: W_k in the reference layout [out x in] (the K-major operand of dfv = dpre . W_k), K4-packed per class.
@@ -700,11 +579,7 @@ extern "C" int bmp_nfp_layer_tile_bwd(const float* dout, const float* out, int n
                                       const float* Wnp, float* dpre, float* dh, hipStream_t st) {
     BMP_REQUIRE(dout && out && n_tiles > 0 && bmp_nfp_layer_supported(d) && csrT_ptr && self_w && deg_class && row_w && Wnp && dpre && dh);
     BMP_REQUIRE((((uintptr_t)dout | (uintptr_t)out | (uintptr_t)Wnp | (uintptr_t)dpre | (uintptr_t)dh) & 15) == 0);
-    const void* fn = d == 128 ? (const void*)k_nfp_tile_bwd<128> : (const void*)k_nfp_tile_bwd<64>;
-    if (int rc = bmp_lds_attr(fn, nfp_tile_lds(d))) return rc;
-    if (d == 128) hipLaunchKernelGGL(k_nfp_tile_bwd<128>, dim3(n_tiles), dim3(512), nfp_tile_lds(d), st, dout, out, csrT_ptr, csrT_col, csrT_val, self_w, deg_class, row_w, Wnp, dpre, dh);
-    else hipLaunchKernelGGL(k_nfp_tile_bwd<64>, dim3(n_tiles), dim3(512), nfp_tile_lds(d), st, dout, out, csrT_ptr, csrT_col, csrT_val, self_w, deg_class, row_w, Wnp, dpre, dh);
-    BMP_LAUNCH_CHECK();
+    WT_LAUNCH(k_nfp_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dout, out, csrT_ptr, csrT_col, csrT_val, self_w, deg_class, row_w, Wnp, dpre, dh);
     return 0;
 }
 
@@ -718,31 +593,28 @@ __global__ __launch_bounds__(512) void k_nfp_readout_tile_fwd(const float* __res
     constexpr int LD = D + 4;
     extern __shared__ float sm[];
     float* ht = sm;
-    float* zt = sm + NFP_T * LD;           // [128][NFP_LDZ]
-    __shared__ int rmol[NFP_T];
-    __shared__ float rw[NFP_T];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row0 = blockIdx.x * NFP_T;
-    for (int i = tid; i < NFP_T * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        *(f32x4*)(ht + r * LD + 4 * q4) = *(const f32x4*)(h + (size_t)(row0 + r) * D + 4 * q4);
-    }
-    if (tid < NFP_T) { rmol[tid] = row_mol[row0 + tid]; rw[tid] = row_w[row0 + tid]; }
+    float* zt = sm + WT_R * LD;            // [128][NFP_LDZ]
+    __shared__ int rmol[WT_R];
+    __shared__ float rw[WT_R];
+    const int tid = threadIdx.x;
+    const WtWave wv = wt_wave(tid);
+    const int lane = wv.lane;
+    const int row0 = blockIdx.x * WT_R;
+    wt_load_tile<D>(ht, h, row0, tid);
+    if (tid < WT_R) { rmol[tid] = row_mol[row0 + tid]; rw[tid] = row_w[row0 + tid]; }
     __syncthreads();
-    const int b = w >> 1;
-    for (int cb = w & 1; cb * 32 < o; cb += 2) {
+    for (int cb = wv.ch; cb * 32 < o; cb += 2) {
         const int c = cb * 32 + (lane & 31);
         const bool valid = c < o;
         f32x16 acc[1];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[0][r] = 0.f;
+        zero_acc(acc);
         // (a column past o multiplies column 0's weights; its results are not stored)
-        nfp_block_mma<1>(acc, ht + (b * 32 + (lane & 31)) * LD + 4 * (lane >> 5), true,
-                         WoTp + ((size_t)(lane >> 5) * o + (valid ? c : 0)) * 4, o, D);
+        wt_block_mma<1, false>(acc, ht + (wv.b * 32 + (lane & 31)) * LD + 4 * (lane >> 5),
+                               WoTp + ((size_t)(lane >> 5) * o + (valid ? c : 0)) * 4, o, D);
         if (valid) {
             const float bc = bo[c];
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) zt[(b * 32 + bmp_acc_row(reg, lane)) * NFP_LDZ + c] = acc[0][reg] + bc;
+            for (int reg = 0; reg < 16; ++reg) zt[wt_row(wv, reg) * NFP_LDZ + c] = acc[0][reg] + bc;
         }
     }
     __syncthreads();
@@ -762,8 +634,8 @@ __global__ __launch_bounds__(512) void k_nfp_readout_tile_fwd(const float* __res
     if (tid < o) {
         float acc = 0.f;
         int cur = -1;
-        for (int r = 0; r <= NFP_T; ++r) {
-            const int m = r < NFP_T ? rmol[r] : -1;
+        for (int r = 0; r <= WT_R; ++r) {
+            const int m = r < WT_R ? rmol[r] : -1;
             if (m != cur) {
                 if (cur >= 0) { float* p = g + (size_t)cur * o + tid; *p = accumulate ? (*p + acc) : acc; }
                 cur = m; acc = 0.f;
@@ -780,8 +652,9 @@ __global__ __launch_bounds__(512) void k_nfp_readout_tile_bwd(const float* __res
     constexpr int NB = D / 64;
     extern __shared__ float sm[];
     float* zt = sm;                        // dz tile [128][NFP_LDZ]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int row0 = blockIdx.x * NFP_T;
+    const int tid = threadIdx.x;
+    const WtWave wv = wt_wave(tid);
+    const int row0 = blockIdx.x * WT_R;
     {
         const int row = tid >> 2, q = tid & 3, gr = row0 + row;
         const int m = row_mol[gr];
@@ -797,19 +670,13 @@ __global__ __launch_bounds__(512) void k_nfp_readout_tile_bwd(const float* __res
         }
     }
     __syncthreads();
-    const int b = w >> 1, ch = w & 1;
     f32x16 acc[NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[nb][r] = 0.f;
-    nfp_block_mma<NB>(acc, zt + (b * 32 + (lane & 31)) * NFP_LDZ + 4 * (lane >> 5), true,
-                      Wnp + ((size_t)(lane >> 5) * D + ch * NB * 32 + (lane & 31)) * 4, D, o);
+    wt_wave_mma<D>(acc, zt, NFP_LDZ, Wnp, o, wv);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        const int c = (ch * NB + nb) * 32 + (lane & 31);
+        const int c = wt_col(wv, NB, nb);
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) dh[(size_t)(row0 + b * 32 + bmp_acc_row(reg, lane)) * D + c] = acc[nb][reg];
+        for (int reg = 0; reg < 16; ++reg) dh[(size_t)(row0 + wt_row(wv, reg)) * D + c] = acc[nb][reg];
     }
 }
 
@@ -819,12 +686,8 @@ extern "C" int bmp_nfp_readout_tile_fwd(const float* h, int n_tiles, int d, int 
                                         const int* row_mol, float* s, float* g, int accumulate, hipStream_t st) {
     BMP_REQUIRE(h && n_tiles > 0 && bmp_nfp_readout_tile_supported(d, o) && WoTp && b && row_w && row_mol && s && g);
     BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WoTp) & 15) == 0);
-    const size_t lds = (size_t)NFP_T * (d + 4 + NFP_LDZ) * sizeof(float);
-    const void* fn = d == 128 ? (const void*)k_nfp_readout_tile_fwd<128> : (const void*)k_nfp_readout_tile_fwd<64>;
-    if (int rc = bmp_lds_attr(fn, lds)) return rc;
-    if (d == 128) hipLaunchKernelGGL(k_nfp_readout_tile_fwd<128>, dim3(n_tiles), dim3(512), lds, st, h, o, WoTp, b, row_w, row_mol, s, g, accumulate);
-    else hipLaunchKernelGGL(k_nfp_readout_tile_fwd<64>, dim3(n_tiles), dim3(512), lds, st, h, o, WoTp, b, row_w, row_mol, s, g, accumulate);
-    BMP_LAUNCH_CHECK();
+    const size_t lds = (size_t)WT_R * (d + 4 + NFP_LDZ) * sizeof(float);
+    WT_LAUNCH(k_nfp_readout_tile_fwd, d, n_tiles, lds, st, h, o, WoTp, b, row_w, row_mol, s, g, accumulate);
     return 0;
 }
 // Wnp: W_o [o x d] (reference layout = the K-major operand of dh = dz . W_o) K4-packed.  ws as bmp_nfp_readout_bwd.
@@ -838,12 +701,8 @@ extern "C" int bmp_nfp_readout_tile_bwd(const float* dg, const float* h, const f
     float* dz = ws;
     float* slab = dz + (size_t)N * o;
     float* cs_ws = ws + (bmp_nfp_readout_bwd_ws_floats(N, d, o) - bmp_colsum_ws_floats(N, o));
-    const size_t lds = (size_t)NFP_T * NFP_LDZ * sizeof(float);
-    const void* fn = d == 128 ? (const void*)k_nfp_readout_tile_bwd<128> : (const void*)k_nfp_readout_tile_bwd<64>;
-    if (int rc = bmp_lds_attr(fn, lds)) return rc;
-    if (d == 128) hipLaunchKernelGGL(k_nfp_readout_tile_bwd<128>, dim3(n_tiles), dim3(512), lds, st, dg, s, o, Wnp, row_w, row_mol, dz, dh);
-    else hipLaunchKernelGGL(k_nfp_readout_tile_bwd<64>, dim3(n_tiles), dim3(512), lds, st, dg, s, o, Wnp, row_w, row_mol, dz, dh);
-    BMP_LAUNCH_CHECK();
+    const size_t lds = (size_t)WT_R * NFP_LDZ * sizeof(float);
+    WT_LAUNCH(k_nfp_readout_tile_bwd, d, n_tiles, lds, st, dg, s, o, Wnp, row_w, row_mol, dz, dh);
     int rc;
     if (o >= 64 && ((uintptr_t)h & 15) == 0) {          // dW_o [d x o] and db on the LDS-staged MFMA weight-gradient GEMM
         WGArgs gw{h, nullptr, d, 0, dz, o, d, o, N, dWT, o, 0};

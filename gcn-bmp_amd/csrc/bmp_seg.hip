@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void k_segpool_bwd(const float* __restrict__ d
             else dA[(size_t)r * o + c] = wr * y * g;
         }
         if (ca == 1) {
-#pragma unroll
-            for (int s = 32; s >= 1; s >>= 1) dot += __shfl_xor(dot, s);
+            dot = bmp_wave_sum(dot);
             if (lane == 0) dA[r] = wr * dot;
         }
     }
@@ -55,12 +54,10 @@ __global__ __launch_bounds__(64) void k_segsoftmax_fwd(const float* __restrict__
     const int r0 = row0[m], nr = nrows[m];
     float mx = -INFINITY;
     for (int k = lane; k < nr; k += 64) if (w[r0 + k] > 0.f) mx = fmaxf(mx, s[r0 + k]);
-#pragma unroll
-    for (int t = 32; t >= 1; t >>= 1) mx = fmaxf(mx, __shfl_xor(mx, t));
+    mx = bmp_wave_max(mx);
     float sum = 0.f;
     for (int k = lane; k < nr; k += 64) if (w[r0 + k] > 0.f) sum += w[r0 + k] * bmp_exp(s[r0 + k] - mx);
-#pragma unroll
-    for (int t = 32; t >= 1; t >>= 1) sum += __shfl_xor(sum, t);
+    sum = bmp_wave_sum(sum);
     for (int k = lane; k < nr; k += 64) alpha[r0 + k] = w[r0 + k] > 0.f ? bmp_exp(s[r0 + k] - mx) / sum : 0.f;
 }
 
@@ -72,8 +69,7 @@ __global__ __launch_bounds__(64) void k_segsoftmax_bwd(const float* __restrict__
     const int r0 = row0[m], nr = nrows[m];
     float t = 0.f;
     for (int k = lane; k < nr; k += 64) t += alpha[r0 + k] * dalpha[r0 + k];
-#pragma unroll
-    for (int q = 32; q >= 1; q >>= 1) t += __shfl_xor(t, q);
+    t = bmp_wave_sum(t);
     for (int k = lane; k < nr; k += 64) ds[r0 + k] = alpha[r0 + k] * (dalpha[r0 + k] - w[r0 + k] * t);
 }
 

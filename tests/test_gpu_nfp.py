@@ -52,6 +52,26 @@ def test_device_derivations_equal_host(pairs):
         assert torch.equal(di[k, :cnt[k]], hi[k, :cnt[k]])
 
 
+def test_deg_rows_across_blocks_equal_host():
+    """Three 256-row blocks and every class 0..7 (the batch above has 1.5 blocks and no row of class 1, 6 or 7): the
+    offsets a block takes from the blocks in front of it, for all seven lists."""
+    from bmp import _lib
+    from bmp._lib import check, ptr, stream
+    from bmp.nfp import deg_rows_host
+    N = 768
+    cls = np.random.RandomState(11).randint(0, 8, N).astype(np.int32)
+    cls[:8] = np.arange(8)
+    L = _lib.lib()
+    dc = torch.from_numpy(cls).to(dev())
+    idx = torch.full((7 * N,), -1, dtype=torch.int32, device=dev())
+    cnt = torch.empty(7, dtype=torch.int32, device=dev())
+    ws = torch.empty(int(L.bmp_nfp_deg_rows_ws_ints(N)), dtype=torch.int32, device=dev())
+    check(L.bmp_nfp_deg_rows(ptr(dc), N, ptr(idx), ptr(cnt), ptr(ws), stream()), "bmp_nfp_deg_rows")
+    hi, hc = deg_rows_host(cls)
+    assert np.array_equal(cnt.cpu().numpy(), hc) and hc.min() > 0
+    assert np.array_equal(idx.cpu().numpy().reshape(7, N), hi)          # (rows past a list's count stay untouched: -1)
+
+
 @pytest.mark.parametrize("hidden,out,layers", [(16, 16, 4), (24, 12, 2), (64, 32, 3), (128, 128, 4)])
 def test_nfp_matches_dense_restatement(pairs, hidden, out, layers):
     from bmp.nfp import NFP
