@@ -25,17 +25,24 @@ def pairs():
     return store, i1, i2, pb
 
 
-@pytest.mark.parametrize("d,o,act", [(16, 16, "tanh"), (128, 128, "tanh"), (24, 12, "identity")])
-def test_nie_coattention_op(pairs, d, o, act):
-    """The co-attention operator alone, on random atom states, vs the packed float64 restatement."""
+@pytest.mark.parametrize("d,o,act,H", [(16, 16, "tanh", 8), (128, 128, "tanh", 8), (24, 12, "identity", 8),
+                                       (24, 12, "tanh", 3), (64, 32, "tanh", 5), (16, 16, "tanh", 15)],
+                         ids=["16-16-tanh", "128-128-tanh", "24-12-identity", "24-12-tanh-H3", "64-32-tanh-H5", "16-16-tanh-H15"])
+def test_nie_coattention_op(pairs, d, o, act, H):
+    """The co-attention operator alone, on random atom states, vs the packed float64 restatement.  H = 8 is a compiled
+    head count; 3, 5 and 15 run the kernels' runtime-head form (15 is the most it takes; 3, 5 and 15 are no multiple of 4,
+    so the head columns of the row layout bmp_coattn_zcols(o, H) end off a 4-column boundary)."""
+    store, i1, i2, pb = pairs
+    _nie_op(pb, len(i1), d, o, act, H)
+
+
+def _nie_op(pb, B, d, o, act, H):
     from bmp.coattention import NieFineCoattention
     from bmp.ggnn import PackedAtoms
     from bmp.snapshot import load_param_dict, grad_dict
-    store, i1, i2, pb = pairs
     pbd = to_dev(pb)
-    B = len(i1)
     dr = O._Draw(d, torch.float64, 0.2)
-    O.init_nie(dr, "", d, o, 8)
+    O.init_nie(dr, "", d, o, H)
     p = {k: v.requires_grad_() for k, v in dr.p.items()}
     g = torch.Generator().manual_seed(d)
     X = (torch.randn(pb.n_rows, d, generator=g, dtype=torch.float64) * (0.3 if act == "identity" else 1.0))
@@ -44,7 +51,7 @@ def test_nie_coattention_op(pairs, d, o, act):
     w1 = torch.randn(B, o, generator=g, dtype=torch.float64); w2 = torch.randn(B, o, generator=g, dtype=torch.float64)
     ((c1 * w1).sum() + (c2 * w2).sum()).backward()
 
-    att = NieFineCoattention(d, o, 8, activation=act).to(dev())
+    att = NieFineCoattention(d, o, H, activation=act).to(dev())
     load_param_dict(att, p)
     Xd = X.float().to(dev()).requires_grad_()
     at = PackedAtoms(Xd, pbd)
@@ -60,10 +67,37 @@ def test_nie_coattention_op(pairs, d, o, act):
         close(gr, p[name].grad, f"grad {name}", floor=floor)
 
 
+def test_nie_coattention_runtime_head_count_on_molecules_larger_than_a_tile():
+    """H = 3 on pairs that hold a 130- and a 300-atom molecule: the pair kernels' global-memory class with the runtime
+    head count."""
+    rs = np.random.RandomState(5)
+    mol = lambda n: synth._make_molecule(rs, n, n, float(n))
+    store = [mol(130), mol(9), mol(300), mol(40)]
+    i1, i2 = np.array([0, 1, 2]), np.array([3, 2, 0])
+    pb = packed.pack_from_store(packed.MolStore(store), [i1, i2], device="cpu")
+    assert pb.oversized and pb.max_rows_per_mol == 301
+    _nie_op(pb, 3, 32, 16, "tanh", 3)
+
+
+def test_nie_coattention_rejects_sixteen_heads():
+    from bmp.coattention import NieFineCoattention
+    with pytest.raises(ValueError):
+        NieFineCoattention(16, 16, 16)
+    NieFineCoattention(16, 16, 15)
+
+
 @pytest.mark.parametrize("d,o", [(16, 16), (64, 32)])
 def test_fourier_nie_coattention_op(pairs, d, o):
     """FourierFineCoattention: the product folds the DFT into the energy operands; the restatement transforms the
     atom states and calls the bilinear form twice (nie_coattention.py:460-505)."""
+    _fourier_op(pairs, d, o, 8)
+
+
+def test_fourier_nie_coattention_runtime_head_count(pairs):
+    _fourier_op(pairs, 64, 32, 5)
+
+
+def _fourier_op(pairs, d, o, H):
     from bmp.coattention import FourierFineCoattention
     from bmp.ggnn import PackedAtoms
     from bmp.snapshot import load_param_dict, grad_dict
@@ -71,7 +105,7 @@ def test_fourier_nie_coattention_op(pairs, d, o):
     pbd = to_dev(pb)
     B = len(i1)
     dr = O._Draw(d + 5, torch.float64, 0.2)
-    O.init_nie(dr, "", d, o, 8)
+    O.init_nie(dr, "", d, o, H)
     p = {k: v.requires_grad_() for k, v in dr.p.items()}
     g = torch.Generator().manual_seed(d)
     X = torch.randn(pb.n_rows, d, generator=g, dtype=torch.float64) * (0.5 / d ** 0.5)    # |DFT| ~ sqrt(d) |x|
@@ -79,7 +113,7 @@ def test_fourier_nie_coattention_op(pairs, d, o):
     c1, c2 = PR.nie_coattention(p, pb, Xr, np.arange(B), B + np.arange(B), activation="tanh", fourier=True)
     w1 = torch.randn(B, o, generator=g, dtype=torch.float64); w2 = torch.randn(B, o, generator=g, dtype=torch.float64)
     ((c1 * w1).sum() + (c2 * w2).sum()).backward()
-    att = FourierFineCoattention(d, o, 8, activation="tanh").to(dev())
+    att = FourierFineCoattention(d, o, H, activation="tanh").to(dev())
     load_param_dict(att, p)
     Xd = X.float().to(dev()).requires_grad_()
     at = PackedAtoms(Xd, pbd)
@@ -95,6 +129,14 @@ def test_fourier_nie_coattention_op(pairs, d, o):
 def test_deep_nie_coattention_op(pairs, n_lt, d, o):
     """Deep / VeryDeep / ExtremeDeep NieFineCoattention: the product folds each side's affine chain into the
     projection operands; the restatement applies the layers one by one (nie_coattention.py:54-59, :155-163)."""
+    _deep_op(pairs, n_lt, d, o, 8)
+
+
+def test_deep_nie_coattention_runtime_head_count(pairs):
+    _deep_op(pairs, 2, 64, 32, 5)
+
+
+def _deep_op(pairs, n_lt, d, o, H):
     from bmp import coattention as C
     from bmp.ggnn import PackedAtoms
     from bmp.snapshot import load_param_dict, grad_dict
@@ -102,7 +144,7 @@ def test_deep_nie_coattention_op(pairs, n_lt, d, o):
     pbd = to_dev(pb)
     B = len(i1)
     dr = O._Draw(d + n_lt, torch.float64, 0.2)
-    O.init_nie(dr, "", d, o, 8, n_lt=n_lt)
+    O.init_nie(dr, "", d, o, H, n_lt=n_lt)
     p = {k: v.requires_grad_() for k, v in dr.p.items()}
     g = torch.Generator().manual_seed(d)
     X = torch.randn(pb.n_rows, d, generator=g, dtype=torch.float64)
@@ -111,7 +153,7 @@ def test_deep_nie_coattention_op(pairs, n_lt, d, o):
     w1 = torch.randn(B, o, generator=g, dtype=torch.float64); w2 = torch.randn(B, o, generator=g, dtype=torch.float64)
     ((c1 * w1).sum() + (c2 * w2).sum()).backward()
     cls = {1: C.DeepNieFineCoattention, 2: C.VeryDeepNieFineCoattention, 3: C.ExtremeDeepNieFineCoattention}[n_lt]
-    att = cls(d, o, 8, activation="tanh").to(dev())
+    att = cls(d, o, H, activation="tanh").to(dev())
     load_param_dict(att, p)
     Xd = X.float().to(dev()).requires_grad_()
     at = PackedAtoms(Xd, pbd)
