@@ -428,7 +428,10 @@ def _linear_wgrad(X, dY, bias=True):
     db = torch.empty(Nout, dtype=torch.float32, device=X.device) if bias else None
     nws = L.bmp_wgrad_ws_floats_c(N, K, Nout)
     ws = _ws(nws, X.device)
-    check(L.bmp_linear_wgrad(ptr(X), K, ptr(dY), Nout, N, K, Nout, ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_linear_wgrad")
+    # (dY may be a block of columns of a wider row-major array: its row stride travels as ldy)
+    if Nout > 1 and dY.stride(1) != 1:
+        raise ValueError("linear wgrad: dY must be row-major with unit column stride")
+    check(L.bmp_linear_wgrad(ptr(X), K, ptr(dY), dY.stride(0), N, K, Nout, ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_linear_wgrad")
     return dWT, db
 
 
@@ -1150,6 +1153,101 @@ def gin_layer(x, W1T, b1, W2T, b2, keep, pb, fused=True):
     if keep is None:
         return LinearRowsFn.apply(t, W2T, b2, ACT["relu"])
     return torch.relu(LinearRowsFn.apply(t, W2T, b2, ACT["identity"]) * keep)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# GGNN step with a fuse gate or a simple gate in the GRU's place (models/ggnn_dev_fuse.py:70-131, models/ggnn_dev_gate.py:73-119;
+# csrc/bmp_gate.hip).
+# ---------------------------------------------------------------------------------------------------------
+GATE_KIND = {"fuse": 0, "gate": 1}
+GATE_PATHS = {"fused": 0, "composed": 0}         # forward calls per form
+
+
+def gate_step_supported(d: int) -> bool:
+    return bool(_lib.lib().bmp_ggnn_gate_step_supported(int(d)))
+
+
+class GateStepFn(Function):
+    """One propagation step -- the GGNN message, then the fuse gate (kind 0) or the simple gate (kind 1) on x = [h, m] -- as ONE
+    fused kernel per tile and direction.  WT [4d x d], bE [4 x d]: the message weights as MsgFn takes them; AU [2d x Nu] K-major,
+    rows [h-part; m-part], columns [z | r | f] (Nu = 3d, fuse) or the gate's (Nu = d); bU [Nu]; keep [N x d] (0 or 1 / (1 - p), the
+    dropout on r * h, fuse only) or None.  d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes go through ``gate_step``."""
+
+    @staticmethod
+    def forward(ctx, h, WT, bE, AU, bU, keep, pb, kind):
+        L = _lib.lib()
+        require_rows(h, "gate step: h")
+        _check_pb(pb, h)
+        N, d = h.shape
+        nu = (3 if kind == 0 else 1) * d
+        if kind not in (0, 1) or tuple(WT.shape) != (4 * d, d) or tuple(bE.shape) != (4, d) or tuple(AU.shape) != (2 * d, nu) \
+                or tuple(bU.shape) != (nu,):
+            raise ValueError("gate step: weight shapes do not match h")
+        if not (whole_tiles_ok(pb) and gate_step_supported(d)):
+            raise ValueError("gate step: the fused kernels take d in {64, 128} on whole tiles; use gate_step()")
+        if kind != 0:
+            keep = None
+        if keep is not None:
+            require_rows(keep, "gate step: keep", d)
+            if keep.shape[0] != N:
+                raise ValueError("gate step: keep must have one row per packed row")
+        bE, bU = bE.contiguous(), bU.contiguous()
+        WTp, AUp = pack_k4(WT), pack_k4(AU)
+        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+        infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
+        m, act, hout = (None, None, f(d)) if infer else (f(d), f(nu), f(d))
+        check(L.bmp_ggnn_gate_step_tile_fwd(kind, ptr(h), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp),
+                                            ptr(bE), ptr(AUp), ptr(bU), ptr(keep), ptr(m), ptr(act), ptr(hout), stream()),
+              "bmp_ggnn_gate_step_tile_fwd")
+        if not infer:
+            ctx.save_for_backward(h, WT, AU, m, act, keep if keep is not None else torch.empty(0))
+        ctx.pb, ctx.kind, ctx.has_keep = pb, kind, keep is not None
+        GATE_PATHS["fused"] += 1
+        return hout
+
+    @staticmethod
+    def backward(ctx, dhout):
+        L = _lib.lib()
+        h, WT, AU, m, act, keep = ctx.saved_tensors
+        pb, kind = ctx.pb, ctx.kind
+        keep = keep if ctx.has_keep else None
+        dhout = dhout.contiguous()
+        N, d = h.shape
+        nu = act.shape[1]
+        Wnat_p, Unat_p = pack_k4(WT.t()), pack_k4(AU.t())
+        dh = torch.empty(N, d, dtype=torch.float32, device=h.device)
+        gda = torch.empty(N, 4 * d + nu, dtype=torch.float32, device=h.device)
+        check(L.bmp_ggnn_gate_step_tile_bwd(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_tiles, d, ptr(pb.csrT_ptr),
+                                            ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p), ptr(dh), ptr(gda), stream()),
+              "bmp_ggnn_gate_step_tile_bwd")
+        o1, cs = _linear_wgrad(h, gda)                               # [d x (4d + Nu)]: dWT as [k][e d + c] | dAU's h half; all column sums
+        o2, _ = _linear_wgrad(m, gda[:, 4 * d:], bias=False)         # dAU's m half
+        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
+        return dh, dWT, cs[:4 * d].reshape(4, d), torch.cat((o1[:, 4 * d:], o2), dim=0), cs[4 * d:], None, None, None
+
+
+def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
+    """One step of the fuse-gate (kind 0) / simple-gate (kind 1) GGNN; the weight layouts are GateStepFn's.  The fused kernels
+    where the tensors are on the GPU, the width is supported and no molecule spans tiles; otherwise the existing operators, for
+    any width that is a multiple of 8: the message operator, the row linear on [h, m] and torch's elementwise operators.  Both are
+    differentiable through autograd."""
+    d = h.shape[1]
+    if kind != 0:
+        keep = None
+    if fused and h.is_cuda and whole_tiles_ok(pb) and gate_step_supported(d):
+        return GateStepFn.apply(h, WT, bE, AU, bU, keep, pb, kind)
+    GATE_PATHS["composed"] += 1
+    m = MsgFn.apply(h, WT, bE, None, None, pb, ACT["identity"])
+    x = torch.cat((h, m), dim=1)
+    if kind != 0:
+        a = LinearRowsFn.apply(x, AU, bU, ACT["sigmoid"])
+        return (1 - a) * h + a * m
+    pre = LinearRowsFn.apply(x, AU, bU, ACT["identity"])
+    z, r, f = torch.tanh(pre[:, :d]), torch.sigmoid(pre[:, d:2 * d]), torch.sigmoid(pre[:, 2 * d:])
+    rh = r * h
+    if keep is not None:
+        rh = rh * keep
+    return rh + f * z
 
 
 # ---------------------------------------------------------------------------------------------------------

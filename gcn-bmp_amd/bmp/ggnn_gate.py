@@ -1,0 +1,167 @@
+"""The two GGNN encoders whose node update is a gate instead of the GRU, with the reference's signatures:
+``models.ggnn_dev_fuse.GGNN`` (models/ggnn_dev_fuse.py:18-168, the recorded "fuse gate" run of RECORD.txt:404-405) as
+``FuseGGNN`` and ``models.ggnn_dev_gate.GGNN`` (models/ggnn_dev_gate.py:20-154) as ``GateGGNN``.  The trainers pick one by
+import (train_ddi_modify_eval2.py:41-43, train_binary.py:39-51).
+
+Both keep models/ggnn.py's embedding, its message (edge type the fastest axis of the 4d output) and its monolithic readout
+``sum over ALL positions of sigmoid(i([h, h0])) * j(h)``; they differ in the update, per atom row, with ``x = [h, m]``:
+
+    fuse (ggnn_dev_fuse.py:72-88,127):  z = tanh(W1 x + b1), r = sigmoid(W2 x + b2), f = sigmoid(W3 x + b3)
+                                        out = dropout(r * h, 0.05) + f * z          (the ratio is hard-wired)
+    gate (ggnn_dev_gate.py:112-116):    a = sigmoid(Wg_k x + bg_k), out = (1 - a) * h + a * m,  k = 0 if update_tying else step
+
+The fuse linears are shared by all steps even when the message weights are untied.  A step is ``Fn.gate_step``: one fused
+kernel per tile and direction at hidden_dim 64 / 128 on whole tiles (csrc/bmp_gate.hip), the composed operators otherwise.
+
+Dropout (the fuse gate's on ``r * h`` and ``dropout_rate`` on every step's output, :157-158): identity under ``eval()``; in
+training the zero-padded positions of a molecule are ONE row of the packed layout and share one mask, where the reference
+draws a mask per padded position -- same expectation, not the same random process.
+
+Parameter names follow the reference link tree (embed.W, message_layers.{i}.W/b, update_layer1|2|3.W/b or gate_layer.{k}.W/b,
+i_layers.{k}.W/b, j_layers.{k}.W/b).  ``FuseGGNN`` also keeps the links the file constructs and never calls -- ``update_layer``
+(the GRU, :55) and ``embed_linear`` (66 -> hidden, :48, reached by float atom features only) -- so a snapshot maps key by key;
+their gradients are zero.
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import functional as Fn
+from .ggnn import EmbedID, GRU, Linear, MAX_ATOMIC_NUM, NUM_EDGE_TYPE, PackedAtoms, _is_float_atoms, as_packed, message_kernel_weights
+
+FUSE_DROPOUT = 0.05             # models/ggnn_dev_fuse.py:127
+
+
+class _GatedGGNN(nn.Module):
+    """What the two files share: constructor checks, embedding, message layers, readout and the step loop."""
+
+    NUM_EDGE_TYPE = NUM_EDGE_TYPE
+    KIND = None                 # Fn.GATE_KIND of the subclass
+    _fused = True               # private switch: False takes the composed operators at every width
+
+    def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
+        super().__init__()
+        if batch_normalization:     # (the files store the flag and never read it; refused like bmp.ggnn.GGNN's)
+            raise NotImplementedError("batch_normalization=True is not supported")
+        if not 0.0 <= dropout_rate < 1.0:
+            raise ValueError("dropout_rate must lie in [0, 1)")
+        if hidden_dim % 8:
+            raise ValueError("hidden_dim must be a multiple of 8 for the MFMA kernels")
+        if out_dim % 4:
+            raise ValueError("out_dim must be a multiple of 4")
+        self.out_dim, self.hidden_dim, self.n_layers = out_dim, hidden_dim, n_layers
+        self.concat_hidden, self.dropout_rate, self.weight_tying = concat_hidden, dropout_rate, weight_tying
+        self.batch_normalization = batch_normalization
+        self.n_readout_layer = n_layers if concat_hidden else 1
+        self.n_message_layer = 1 if weight_tying else n_layers
+        self.embed = EmbedID(out_size=hidden_dim, in_size=n_atom_types)
+        self.message_layers = nn.ModuleList([Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
+        self.atoms = None
+
+    def _make_readout(self):
+        self.i_layers = nn.ModuleList([Linear(2 * self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
+        self.j_layers = nn.ModuleList([Linear(self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
+
+    def plannable(self) -> bool:
+        return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
+
+    def readout(self, h, h0, pb, step=0):
+        """:133-141: i sees [h, h0], j sees h only -> j's h0 rows are zero in the kernel layout."""
+        i, j = self.i_layers[step if self.concat_hidden else 0], self.j_layers[step if self.concat_hidden else 0]
+        d = self.hidden_dim
+        WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
+        return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
+
+    def _update_weights(self, step):
+        """(AU [2d x Nu], bU [Nu]) of the step, in Fn.gate_step's layout."""
+        raise NotImplementedError
+
+    def forward(self, atom_array, adj=None):
+        """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
+        ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
+        if _is_float_atoms(atom_array):
+            raise NotImplementedError("float atom features (embedding bypass, models/ggnn_dev_fuse.py:149-150, "
+                                      "models/ggnn_dev_gate.py:136-137) are not supported")
+        pb = as_packed(atom_array, adj, self.embed.W.device)
+        pb.check_atom_ids(self.embed.W.shape[0])
+        h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+        h0 = h
+        fuse = self.KIND == Fn.GATE_KIND["fuse"]
+        # (tests inject the fuse gate's training masks: one (n_rows, hidden) tensor per step)
+        masks = getattr(self, "_dropout_masks", None) if (self.training and fuse) else None
+        if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
+            raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
+        msgw, updw, g_list = {}, {}, []
+        for step in range(self.n_layers):
+            li = 0 if self.weight_tying else step
+            if li not in msgw:
+                msgw[li] = message_kernel_weights(self.message_layers[li])
+            ui = self._update_index(step)
+            if ui not in updw:
+                updw[ui] = self._update_weights(ui)
+            keep = None
+            if fuse and self.training:
+                if masks is not None:
+                    keep = masks[step]
+                else:
+                    keep = (torch.rand(h.shape, device=h.device) >= FUSE_DROPOUT).to(torch.float32) * (1.0 / (1.0 - FUSE_DROPOUT))
+            h = Fn.gate_step(h, *msgw[li], *updw[ui], self.KIND, keep, pb, self._fused)
+            if self.dropout_rate != 0.0 and self.training:              # :157-158, chainer: mask / (1 - ratio)
+                h = torch.nn.functional.dropout(h, p=self.dropout_rate, training=True)
+            if self.concat_hidden:
+                g_list.append(self.readout(h, h0, pb, step))
+        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+        if self.concat_hidden:
+            return torch.cat(g_list, dim=1)
+        return self.readout(h, h0, pb, 0)
+
+    def _update_index(self, step):
+        return 0
+
+    def get_atom_array(self):
+        """Not in the two files: the last step's atom states, so that the encoders compose with every co-attention (as
+        models/ggnn_att.py:662-664 does for the GRU form)."""
+        assert self.atoms is not None
+        return self.atoms
+
+
+class FuseGGNN(_GatedGGNN):
+    """models/ggnn_dev_fuse.py:18-168."""
+
+    KIND = Fn.GATE_KIND["fuse"]
+
+    def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
+                 batch_normalization=False, weight_tying=True):
+        super().__init__(out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying)
+        self.embed_linear = Linear(66, hidden_dim)                      # :48, never reached with atom ids
+        self.update_layer = GRU(2 * hidden_dim, hidden_dim)             # :55, constructed and never called (:126)
+        self.update_layer1 = Linear(2 * hidden_dim, hidden_dim)         # z
+        self.update_layer2 = Linear(2 * hidden_dim, hidden_dim)         # r
+        self.update_layer3 = Linear(2 * hidden_dim, hidden_dim)         # f
+        self._make_readout()
+
+    def _update_weights(self, step):
+        ls = (self.update_layer1, self.update_layer2, self.update_layer3)
+        return torch.cat([l.W for l in ls], dim=0).t().contiguous(), torch.cat([l.b for l in ls])
+
+
+class GateGGNN(_GatedGGNN):
+    """models/ggnn_dev_gate.py:20-154."""
+
+    KIND = Fn.GATE_KIND["gate"]
+
+    def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
+                 batch_normalization=False, weight_tying=True, update_tying=True):
+        super().__init__(out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying)
+        self.update_tying = update_tying
+        self.n_update_layer = 1 if update_tying else n_layers
+        self.gate_layer = nn.ModuleList([Linear(2 * hidden_dim, hidden_dim) for _ in range(self.n_update_layer)])
+        self._make_readout()
+
+    def _update_index(self, step):
+        return 0 if self.update_tying else step
+
+    def _update_weights(self, step):
+        lin = self.gate_layer[step]
+        return lin.W.t().contiguous(), lin.b

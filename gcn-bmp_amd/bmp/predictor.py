@@ -164,6 +164,10 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
         # the trainer does not hand its weight-tying option to GIN: tied (ONE layer runs) unless asked for by keyword here
         enc = GIN(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, dropout_ratio=dropout_ratio, concat_hidden=True,
                   weight_tying=weight_tying)
+    elif encoder in ("ggnn-fuse", "ggnn-gate"):      # train_ddi_modify_eval2.py:41-43, train_binary.py:39-51: chosen by import there
+        from .ggnn_gate import FuseGGNN, GateGGNN
+        cls = FuseGGNN if encoder == "ggnn-fuse" else GateGGNN
+        enc = cls(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
     else:
         raise ValueError('[ERROR] Invalid graph embedding encoder.')
     a = None

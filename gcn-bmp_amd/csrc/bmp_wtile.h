@@ -1,6 +1,7 @@
-// Whole-tile machinery shared by the fused per-tile kernels of the GIN and NFP encoders (bmp_gin.hip, bmp_nfp.hip): one
-// workgroup of 512 threads (8 waves) per 128-row tile, d in {64, 128}, exact-f32 MFMA 32x32x2, two [128][d + 4] tiles in
-// LDS used in turn; wave w owns the 32-row block w >> 1 of the operand tile and the column half w & 1 of the product.
+// Whole-tile machinery shared by the fused per-tile kernels of the GIN, NFP and gated-GGNN encoders (bmp_gin.hip, bmp_nfp.hip,
+// bmp_gate.hip): one workgroup of 512 threads (8 waves) per 128-row tile, d in {64, 128}, exact-f32 MFMA 32x32x2, two
+// [128][d + 4] tiles in LDS used in turn; wave w owns the 32-row block w >> 1 of the operand tile and the column half w & 1 of
+// the product.
 // Weights are K4-packed ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
 // (The half-tile-group kernels of bmp_fused*.hip keep their own loop and gather in bmp_tile.h: tile_mma, tile_gather.)
 #pragma once
@@ -48,6 +49,29 @@ __device__ __forceinline__ void wt_block_mma(f32x16 (&acc)[NB], const float* Ar,
     }
 }
 
+// The same for NG groups of output columns that share the A rows (the gates of one update, the two halves of its transpose):
+// acc[g][nb] += A(32 rows x K) . B(K x 32 cols), the column of (g, nb) = first column + g * gs + nb * 32 of a packed matrix
+// Nw columns wide.  One A fragment feeds NG * NB MFMAs.
+template <int NG, int NB>
+__device__ __forceinline__ void wt_block_mma_g(f32x16 (&acc)[NG][NB], const float* Ar, const float* __restrict__ Bp, int Nw, int gs,
+                                               int K) {
+#pragma unroll 2
+    for (int k0 = 0; k0 < K; k0 += 8) {
+        const f32x4 a = *(const f32x4*)(Ar + k0);
+        f32x4 b[NG][NB];
+#pragma unroll
+        for (int g = 0; g < NG; ++g)
+#pragma unroll
+            for (int nb = 0; nb < NB; ++nb) b[g][nb] = *(const f32x4*)(Bp + ((size_t)(k0 >> 2) * Nw + g * gs + nb * 32) * 4);
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int g = 0; g < NG; ++g)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) acc[g][nb] = bmp_mfma(a[t], b[g][nb][t], acc[g][nb]);
+    }
+}
+
 // One wave's product, opened: acc = 0, and this lane's addresses into rows [32 b, 32 b + 32) of `opnd` (row stride lda) and
 // into the columns of half ch of a packed [K x D] matrix (boff: floats from the matrix's base).
 struct WtLane { const float* Ar; size_t boff; };
@@ -86,6 +110,30 @@ __device__ __forceinline__ void wt_tile_gather(f32x4 (&acc)[D / 16], const float
 #pragma unroll
         for (int f = 0; f < F; ++f) acc[f] += *(const f32x4*)(s + 4 * f) * v;
     }
+}
+
+// ... and filtered by bond type: the sum over the row's entries of type e (col & 3) of val * src[col - row0], no self term.
+// Returns the row's weighted degree for the type (the sum of those entries' values).
+template <int D>
+__device__ __forceinline__ float wt_tile_gather_typed(f32x4 (&acc)[D / 16], const float* src, int row, int q, int row0,
+                                                      const int* __restrict__ ptr, const int* __restrict__ col,
+                                                      const float* __restrict__ val, int e) {
+    constexpr int LD = D + 4, F = D / 16;
+#pragma unroll
+    for (int f = 0; f < F; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    float wd = 0.f;
+    for (int ed = ptr[row0 + row]; ed < ptr[row0 + row + 1]; ++ed) {
+        const int cv = col[ed];
+        if ((cv & 3) != e) continue;
+        const int j = (cv >> 2) - row0;
+        if ((unsigned)j >= (unsigned)WT_R) continue;          // (molecules never straddle a tile on this path: never taken)
+        const float v = val[ed];
+        const float* s = src + j * LD + q * (D / 4);
+#pragma unroll
+        for (int f = 0; f < F; ++f) acc[f] += *(const f32x4*)(s + 4 * f) * v;
+        wd += v;
+    }
+    return wd;
 }
 
 // Pick the <64> / <128> instance of a tile kernel, set its LDS attribute (once per device), launch one workgroup per tile,

@@ -209,6 +209,31 @@ int bmp_gin_layer_tile_bwd(const float* dout, const float* out, const float* kee
                            const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* W2np, const float* W1np,
                            float* dp2, float* dp1, float* dh, bmp_stream_t stream);
 
+/* ---- GGNN step with a fuse gate or a simple gate in the GRU's place -- models/ggnn_dev_fuse.py:70-131,
+ * models/ggnn_dev_gate.py:73-119 (csrc/bmp_gate.hip) ----
+ * The message is bmp_ggnn_step_fwd's: m = sum_e (agg_e . W_e + wdeg_e b_e).  The update reads x = [h, m]:
+ *   kind 0 (fuse): z = tanh(x W1^T + b1), r = sigmoid(x W2^T + b2), f = sigmoid(x W3^T + b3); out = keep * (r * h) + f * z
+ *   kind 1 (gate): a = sigmoid(x Wg^T + bg); out = (1 - a) * h + a * m
+ * keep [N x d]: the dropout mask on r * h, 0 or 1 / (1 - p) per element, read for kind 0 only; a null pointer means no dropout.
+ * One kernel per direction, one workgroup per 128-row tile, d with bmp_ggnn_gate_step_supported (64 or 128), exact-f32 MFMA; whole
+ * tiles whose molecules never straddle a tile (no tile table).  N = 128 n_tiles, Nu = 3d (kind 0) or d (kind 1).
+ * fwd: WTp [4d x d] and bE [4 x d] as for bmp_ggnn_step_fwd; AUp [2d x Nu] K-major, rows [h-part; m-part], columns [z | r | f]
+ *      (kind 0) or the gate's (kind 1), K4-packed; bU [Nu].  Saves m [N x d] and act [N x Nu], the activations z | r | f or a
+ *      (m and act may be NULL together: forward-only evaluation), and writes hout [N x d].
+ * bwd: Wnat_p [d x 4d] as for bmp_ggnn_step_bwd; Unat_p [Nu x 2d] = AU^T, K4-packed.  Writes dh [N x d] and
+ *      gda [N x (4d + Nu)] = [G_0 .. G_3 | dpre]: G_e the transposed-CSR gather of dm over the bonds of type e, dpre the gradient
+ *      at the update's pre-activations -- the column order of bmp_ggnn_step_bwd's gda.
+ * Weight gradients: two calls of bmp_linear_wgrad (deterministic, no atomics) -- X = h, dY = gda at full width gives dWT
+ * ([k][e d + c]), the h half of dAU and all the column sums (dbE | dbU); X = m, dY = gda + 4d (ldy = 4d + Nu, Nu columns) gives
+ * the m half of dAU.  No allocation, no host sync; every row array 16-byte aligned. */
+int bmp_ggnn_gate_step_supported(int d);
+int bmp_ggnn_gate_step_tile_fwd(int kind, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col,
+                                const float* csr_val, const float* WTp, const float* bE, const float* AUp, const float* bU,
+                                const float* keep, float* m, float* act, float* hout, bmp_stream_t stream);
+int bmp_ggnn_gate_step_tile_bwd(int kind, const float* dhout, const float* h, const float* m, const float* act, const float* keep,
+                                int n_tiles, int d, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
+                                const float* Wnat_p, const float* Unat_p, float* dh, float* gda, bmp_stream_t stream);
+
 /* ---- Neural-fingerprint encoder -- models/models/nfp.py (csrc/bmp_nfp.hip) ----
  * ONE adjacency: every bond counts once whatever its type (csr_col >> 2 is the source row), plus a self loop of weight
  * self_w [N] on the rows that have one (1 on real atoms, 0 on pad and dead rows).  deg_class [N] in 0..7: k when the COLUMN
