@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import check, ptr, stream
 from .coattention import Bilinear
 from .ggnn import Linear
-from .mlp import MLPFn
+from .mlp import MLPFn, kernels_take
 
 SYM, HOLE, DISTMULT, NTN_KIND = 0, 1, 2, 3
 
@@ -63,8 +63,14 @@ class PairFeatFn(Function):
 
 
 def _tail(layers, l_out, h):
+    """The relu-MLP behind the pair feature: bmp_mlp_fwd / _bwd where they take the shape (bmp.mlp.kernels_take), the plain
+    torch ops on the device tensors otherwise, as in MLP.forward."""
     ls = list(layers) + [l_out]
-    return MLPFn.apply(None, h, None, None, None, *[l.W for l in ls], *[l.b for l in ls])
+    if kernels_take([h.shape[1]] + [l.out_size for l in ls]):
+        return MLPFn.apply(None, h, None, None, None, *[l.W for l in ls], *[l.b for l in ls])
+    for l in layers:
+        h = torch.relu(torch.nn.functional.linear(h, l.W, l.b))
+    return torch.nn.functional.linear(h, l_out.W, l_out.b)
 
 
 def _check_act(activation):

@@ -14,7 +14,30 @@ from torch.autograd import Function
 
 from .ggnn import Linear
 
+# Limits of csrc/bmp_mlp.hip (MLP_MAXL, MLP_MAXW, MLP_MAXIN) and the LDS the launches share with their weights: a workgroup
+# has 160 KB; k_mlp_fwd keeps 64 KB of row buffers beside the first layer's weights, k_mlp_sce reserves 48 KB beside the
+# weights of every layer.  The first layer's weights [w1 x in] lie there transposed, in * (w1 + 1) floats; a later layer's
+# [no x ni] as they are with rows padded by one, no * (ni + 1) floats.
 _MAXL, _MAXW, _MAXIN = 4, 64, 1024
+_LDS_BYTES = 160 * 1024
+_FWD_ROWS_BYTES = 65536
+_SCE_ROWS_BYTES = 49152
+
+
+def kernels_take(dims) -> bool:
+    """Do bmp_mlp_fwd / bmp_mlp_bwd take an MLP of the widths ``dims`` = [input, hidden..., output]?  The number of Linear
+    layers, the widths, and the first layer's weights beside the forward launch's row buffers in LDS."""
+    nl = len(dims) - 1
+    if not 1 <= nl <= _MAXL or any(d is None or d <= 0 for d in dims):
+        return False
+    return (dims[0] <= _MAXIN and all(w <= _MAXW for w in dims[1:])
+            and 4 * dims[0] * (dims[1] + 1) + _FWD_ROWS_BYTES <= _LDS_BYTES)
+
+
+def head_kernel_takes(dims) -> bool:
+    """bmp_mlp_sce_fwdbwd on top of ``kernels_take``: the weights of ALL layers beside 48 KB of row buffers."""
+    return kernels_take(dims) and 4 * (dims[0] * (dims[1] + 1) + sum(dims[k + 1] * (dims[k] + 1) for k in range(1, len(dims) - 1))) \
+        + _SCE_ROWS_BYTES <= _LDS_BYTES
 
 
 def _parr(tensors):
@@ -244,11 +267,12 @@ class MLP(nn.Module):
     def _linears(self):
         return list(self.layers) + [self.l_out]
 
-    def _kernel_ok(self) -> bool:
-        ls = self._linears()
-        return (self.activation in (torch.relu, torch.nn.functional.relu) and len(ls) <= _MAXL and self.in_dim is not None
-                and self.in_dim <= _MAXIN
-                and all(l.out_size <= _MAXW for l in ls))
+    def _kernel_ok(self, head: bool = False) -> bool:
+        """The MLP kernels take this module (``head``: the one-launch classifier form as well)."""
+        if self.activation not in (torch.relu, torch.nn.functional.relu) or self.in_dim is None:
+            return False
+        dims = [self.in_dim] + [l.out_size for l in self._linears()]
+        return head_kernel_takes(dims) if head else kernels_take(dims)
 
     # ---- layout plan protocol (bmp/plan.py): identity layouts, the kernels write the gradients in place ----
     def plannable(self) -> bool:
@@ -304,11 +328,8 @@ class MLP(nn.Module):
         predictor (train_ddi_modify.py:284-286).  On the device, with gradients on, one launch each way (MLPLossFn); otherwise
         ``forward`` followed by ``sigmoid_cross_entropy``."""
         ls = self._linears()
-        dims = [self.in_dim] + [l.out_size for l in ls]
-        # (the launch keeps every layer's weights in LDS beside 48 KB of row buffers)
-        fits = self.in_dim is not None and 4 * (dims[0] * (dims[1] + 1) + sum(dims[k + 1] * (dims[k] + 1) for k in range(1, len(ls)))) \
-            <= 160 * 1024 - 49152
-        if x.is_cuda and torch.is_grad_enabled() and fits and self._kernel_ok() and \
+        # (the launch keeps every layer's weights in LDS beside 48 KB of row buffers: its own budget on top of forward's)
+        if x.is_cuda and torch.is_grad_enabled() and self._kernel_ok(head=True) and \
                 x.shape[-1] + (0 if x2 is None else x2.shape[-1]) == self.in_dim:
             fast = getattr(self, "_fast", None)
             if fast is not None:

@@ -31,6 +31,37 @@ def close(got, want, name, tol=1e-4, floor=1e-6):
     return rel
 
 
+def bound_ratio(got, want, bound):
+    """(worst err / bound over the elements, err there, bound there): 0 / 0 counts as 0, err > 0 against 0 as inf."""
+    got, want, bound = (t.detach().double().cpu() for t in (got, want, bound))
+    if not got.numel():
+        return 0.0, 0.0, 0.0
+    err = (got - want).abs()
+    q = torch.where(err == 0, torch.zeros_like(err), err / bound).reshape(-1)      # err / 0 = inf
+    q = torch.where(torch.isnan(q), torch.full_like(q, float("inf")), q)          # a non-finite result is outside any bound
+    k = int(q.argmax())
+    return q[k].item(), err.reshape(-1)[k].item(), bound.reshape(-1)[k].item()
+
+
+def close_bound(got, want, bound, name):
+    """Element-wise form of ``close``: asserts |got - want| <= bound for EVERY element (``bound`` a tensor of the shape of
+    ``want``, e.g. tests/link_ref.py's r * 2**-24 * S) and records the worst achieved err / bound in the same log with the
+    same keys: ``rel`` is that ratio and ``tol`` 1, ``abs`` and ``scale`` the error and the bound of the worst element."""
+    assert got.shape == want.shape == bound.shape, f"{name}: shapes {tuple(got.shape)} {tuple(want.shape)} {tuple(bound.shape)}"
+    rel, err, scale = bound_ratio(got, want, bound)
+    test = os.environ.get("PYTEST_CURRENT_TEST", "?").split(" ")[0]
+    print(f"[parity] {name}: worst err / bound {rel:.3e} (err {err:.3e}, bound {scale:.3e})")
+    try:
+        os.makedirs(os.path.dirname(LOG), exist_ok=True)
+        with open(LOG, "a") as f:
+            f.write(json.dumps(dict(test=test, name=name, rel=rel, abs=err, scale=scale, tol=1.0)) + "\n")
+    except OSError:
+        pass
+    assert torch.isfinite(got).all(), f"{name}: non-finite values"
+    assert rel <= 1.0, f"{name}: an element is {rel:.3e} x its bound (err {err:.3e}, bound {scale:.3e})"
+    return rel
+
+
 def summarize():
     """worst achieved relative error per test -> gpurun_out/parity_summary.json"""
     if not os.path.exists(LOG):

@@ -92,3 +92,57 @@ def test_classifier_form_of_the_mlp_on_host_tensors_is_forward_plus_loss():
     assert torch.equal(y, y0) and torch.equal(loss, sigmoid_cross_entropy(y0, t))
     loss.backward()
     assert g1.grad is not None and torch.isfinite(g1.grad).all()
+
+
+def test_mlp_kernel_predicate_arithmetic():
+    """bmp.mlp.kernels_take: layers, widths, and the first layer's weights -- in * (w1 + 1) floats -- beside the 64 KB of row
+    buffers of bmp_mlp_fwd in 160 KB of LDS, i.e. at most 24576 floats; head_kernel_takes: all weights within 28672 floats."""
+    from bmp.mlp import head_kernel_takes, kernels_take
+    assert kernels_take([1024, 23, 2]) and 1024 * 24 == 24576
+    assert kernels_take([768, 31, 2]) and 768 * 32 == 24576
+    assert not kernels_take([1024, 24, 2])
+    assert not kernels_take([512, 64, 16, 1]) and 512 * 65 == 33280
+    assert kernels_take([378, 64, 16, 1]) and not kernels_take([379, 64, 16, 1])
+    assert kernels_take([1024, 1]) and not kernels_take([1025, 1])
+    assert kernels_take([8, 64, 64, 64, 64]) and not kernels_take([8, 65, 1]) and not kernels_take([8, 16, 65])
+    assert not kernels_take([8, 16, 16, 16, 16, 1]) and not kernels_take([8]) and not kernels_take([None, 16, 1])
+    assert head_kernel_takes([384, 63, 64]) and 4 * (384 * 64 + 64 * 64) == 160 * 1024 - 49152
+    assert kernels_take([384, 63, 64, 1]) and not head_kernel_takes([384, 63, 64, 1])
+    assert not head_kernel_takes([1024, 24, 2])               # never wider than the tail's own kernels
+
+
+def test_mlp_predicate_constants_are_the_kernels():
+    import os
+    import re
+    from bmp import mlp as M
+    src = open(os.path.join(os.path.dirname(M.__file__), "..", "csrc", "bmp_mlp.hip")).read()
+    D = {k: int(v) for k, v in re.findall(r"#define (MLP_[A-Z]+) (\d+)", src)}
+    assert (M._MAXL, M._MAXW, M._MAXIN) == (D["MLP_MAXL"], D["MLP_MAXW"], D["MLP_MAXIN"])
+    assert M._FWD_ROWS_BYTES == 2 * D["MLP_FR"] * D["MLP_MAXIN"] * 4          # k_mlp_fwd: buf[2][MLP_FR][MLP_MAXIN]
+    assert f"wt_bytes + {M._FWD_ROWS_BYTES} <= 160 * 1024" in src and f"wt_bytes + {M._SCE_ROWS_BYTES} <= 160 * 1024" in src
+    assert M._LDS_BYTES == 160 * 1024
+    # k_mlp_sce's row buffers: xin, hid, dcur and a few words, inside what it reserves
+    static = 4 * D["MLP_BR"] * (D["MLP_MAXIN"] + (D["MLP_MAXL"] + 2) * D["MLP_MAXW"]) + 64
+    assert static <= M._SCE_ROWS_BYTES
+
+
+def test_mlp_that_does_not_fit_is_not_plannable_and_takes_the_plain_ops():
+    """plannable() is the predicate of forward: a shape bmp_mlp_fwd would refuse is never planned, so the planned path
+    records no launch that would be refused; link._tail asks the same predicate."""
+    from bmp import link
+    from bmp.mlp import MLP
+    assert MLP(1, (32, 16), in_dim=256).plannable()
+    for m in (MLP(1, (64, 16), in_dim=512), MLP(1, (32, 16), in_dim=1024), MLP(1, (128,), in_dim=16),
+              MLP(1, (16, 16, 16, 16), in_dim=16)):
+        assert not m.plannable() and not m._kernel_ok() and not m._kernel_ok(head=True)
+    lazy = MLP(1, (32, 16))
+    assert not lazy.plannable()
+    lazy.materialize_input(128)
+    assert lazy.plannable()
+    # outside the predicate the tail of the link predictors is the plain ops (host tensors serve: no kernel is asked)
+    torch.manual_seed(0)
+    lp = link.NTN(16, 16, 1, hidden_dims=(128,))
+    h = torch.randn(5, 8)
+    want = torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(h, lp.mlp_layers[0].W, lp.mlp_layers[0].b)),
+                                      lp.l_out.W, lp.l_out.b)
+    assert torch.equal(link._tail(lp.mlp_layers, lp.l_out, h), want)
