@@ -102,6 +102,7 @@ SIGNATURES = {
     "bmp_collate_plan_enc": (_I, [_P, _P, _I, _P, _I, _I, _I, _I] + [_P] * 11),
     "bmp_bimpm_supported": (_I, [_I, _I, _I]),
     "bmp_bimpm_ws_floats": (_Z, [_I, _I, _I, _I, _I]),
+    "bmp_bimpm_ws_layout": (_I, [_I, _I, _I, _I, _P]),
     "bmp_bimpm_fwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bmp_bimpm_bwd": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
     "bmp_encrows_expand": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P]),

@@ -16,6 +16,7 @@
 // Plain fp32 FMA work (no matrix-core shape: the perspectives scale the feature axis inside every dot product), fixed
 // summation orders, no atomics: bitwise reproducible.  The backward recomputes the forward of its pair (same code, same
 // order, so the same maxima win) and distributes gradients by owner-computes loops.
+#include <stdint.h>
 #include <string.h>
 #include "bmp_common.h"
 
@@ -66,7 +67,7 @@ __host__ __device__ static inline size_t bm_scratch_floats(int maxn, int d, int 
     return s + 64;
 }
 
-__device__ static inline BmScr bm_carve(float* p, int maxn, int d, int H, bool bwd) {
+__host__ __device__ static inline BmScr bm_carve(float* p, int maxn, int d, int H, bool bwd) {
     BmScr s;
     const size_t n = (size_t)maxn, nH = n * H, nd = n * d;
     s.nP1 = p; p += nH; s.nQ1 = p; p += nH; s.nR1 = p; p += nH; s.nP2 = p; p += nH; s.nQ2 = p; p += nH; s.nR2 = p; p += nH;
@@ -444,8 +445,25 @@ static size_t bm_stage_floats(int maxn, int d) { return bm_in_lds(maxn, d) ? 0 :
 // Any molecule size: pairs that fit stage their rows in LDS, larger ones in the workspace (bmp_bimpm_ws_floats grows).
 extern "C" int bmp_bimpm_supported(int d, int H, int maxn) { return d > 0 && H > 0 && maxn > 0; }
 
+// floats of one workgroup's scratch slice: the carve-up, then the staged rows of the global-memory class
+static size_t bm_per_wg_floats(int maxn, int d, int H, bool bwd) { return bm_scratch_floats(maxn, d, H, bwd) + bm_stage_floats(maxn, d); }
+
 extern "C" size_t bmp_bimpm_ws_floats(int d, int H, int maxn, int B, int backward) {
-    return (size_t)bm_grid(B) * (bm_scratch_floats(maxn, d, H, backward != 0) + bm_stage_floats(maxn, d) + (backward ? (size_t)3 * H * d : 0));
+    return (size_t)bm_grid(B) * (bm_per_wg_floats(maxn, d, H, backward != 0) + (backward ? (size_t)3 * H * d : 0));
+}
+
+// Where a launch keeps its maxima (for tests that pin gradients to the selections the kernel made): out[0] = floats between
+// two workgroups' slices of ws, out[1..4] = float offsets of jT2, iT1 ([n x d]) and j1s, i2s ([n x H], n = the pair's own row
+// count, not maxn) within a slice; int32 in the float slots.  Workgroup g handles pairs g, g + grid, ...: with B <= 512 slice
+// pr holds pair pr after a launch.  Read off the carve-up the kernel itself uses (an address that is never dereferenced).
+extern "C" int bmp_bimpm_ws_layout(int d, int H, int maxn, int backward, size_t* out) {
+    BMP_REQUIRE(out && bmp_bimpm_supported(d, H, maxn));
+    float* const base = reinterpret_cast<float*>((uintptr_t)1 << 20);
+    const BmScr s = bm_carve(base, maxn, d, H, backward != 0);
+    out[0] = bm_per_wg_floats(maxn, d, H, backward != 0);
+    out[1] = (size_t)((float*)s.jT2 - base); out[2] = (size_t)((float*)s.iT1 - base);
+    out[3] = (size_t)((float*)s.j1s - base); out[4] = (size_t)((float*)s.i2s - base);
+    return 0;
 }
 
 static int bm_fill(BmArgs& a, const float* X1, const float* X2, int d, int H, const float* w1, const int* r1, const int* n1,
@@ -456,7 +474,7 @@ static int bm_fill(BmArgs& a, const float* X1, const float* X2, int d, int H, co
     BMP_REQUIRE(bmp_bimpm_supported(d, H, maxn));
     a.X1 = X1; a.X2 = X2; a.d = d; a.H = H; a.B = B; a.w1 = w1; a.w2 = w2; a.r1 = r1; a.n1 = n1; a.r2 = r2; a.n2 = n2;
     a.P = P; a.Q = Q; a.R = R; a.maxn = maxn;
-    a.scratch = ws; a.scratch_per_wg = bm_scratch_floats(maxn, d, H, bwd) + bm_stage_floats(maxn, d);
+    a.scratch = ws; a.scratch_per_wg = bm_per_wg_floats(maxn, d, H, bwd);
     a.stage_global = bm_in_lds(maxn, d) ? 0 : 1; a.stage_off = bm_scratch_floats(maxn, d, H, bwd);
     return 0;
 }

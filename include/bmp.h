@@ -389,6 +389,9 @@ int bmp_coattn_nie_bwd(const float* dout1, const float* dout2, const float* X1, 
  * forward (same order: the same maxima win) and overwrites dP, dQ, dR and the rows of dX1 / dX2 that belong to a pair. */
 int bmp_bimpm_supported(int d, int H, int maxn);
 size_t bmp_bimpm_ws_floats(int d, int H, int maxn, int B, int backward);
+/* out[0] = floats per workgroup slice of ws, out[1..4] = float offsets within a slice of the int32 arg-max arrays jT2, iT1
+ * ([n x d], attentive max) and j1s, i2s ([n x H], max-pooling matching); with B <= 512, slice pr is pair pr's after a launch. */
+int bmp_bimpm_ws_layout(int d, int H, int maxn, int backward, size_t* out);
 int bmp_bimpm_fwd(const float* X1, const float* X2, int d, int H, const float* w1, const int* r1, const int* n1, const float* w2,
                   const int* r2, const int* n2, int B, int maxn, const float* P, const float* Q, const float* R, float* out1,
                   float* out2, float* ws, size_t ws_floats, bmp_stream_t stream);
