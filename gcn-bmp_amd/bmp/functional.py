@@ -1251,6 +1251,86 @@ def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# GGNN step with a per-atom self loop in the message (models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py;
+# csrc/bmp_loop.hip).
+# ---------------------------------------------------------------------------------------------------------
+LOOP_PATHS = {"fused": 0, "composed": 0}         # forward calls per form
+
+
+def loop_step_supported(d: int) -> bool:
+    return bool(_lib.lib().bmp_ggnn_loop_step_supported(int(d)))
+
+
+class LoopStepFn(Function):
+    """One propagation step -- the GGNN message plus the self loop h . WsT + bs, then the GRU on [h, m] -- as ONE fused kernel per
+    tile and direction.  WT [4d x d], bE [4 x d], AT [2d x 3d], UcT [d x d], b [3d]: as GGNNStepFn takes them (GRU.kernel_weights);
+    WsT [d x d] K-major (the transposed self-loop weight), bs [d].  d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes
+    go through ``loop_step``."""
+
+    @staticmethod
+    def forward(ctx, h, WT, bE, WsT, bs, AT, UcT, b, pb, first):
+        L = _lib.lib()
+        require_rows(h, "loop step: h")
+        _check_pb(pb, h)
+        N, d = h.shape
+        if tuple(WT.shape) != (4 * d, d) or tuple(bE.shape) != (4, d) or tuple(WsT.shape) != (d, d) or tuple(bs.shape) != (d,) \
+                or tuple(AT.shape) != (2 * d, 3 * d) or tuple(UcT.shape) != (d, d) or tuple(b.shape) != (3 * d,):
+            raise ValueError("loop step: weight shapes do not match h")
+        if not (whole_tiles_ok(pb) and loop_step_supported(d)):
+            raise ValueError("loop step: the fused kernels take d in {64, 128} on whole tiles; use loop_step()")
+        bE, bs, b = bE.contiguous(), bs.contiguous(), b.contiguous()
+        WTp, WsTp, ATp, UcTp = pack_k4(WT), pack_k4(WsT), pack_k4(AT), pack_k4(UcT)
+        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+        infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
+        m, rz, c, hout = (None, None, None, f(d)) if infer else (f(d), f(2 * d), f(d), f(d))
+        check(L.bmp_ggnn_loop_step_tile_fwd(ptr(h), pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                                            ptr(WTp), ptr(bE), ptr(WsTp), ptr(bs), ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c),
+                                            ptr(hout), stream()), "bmp_ggnn_loop_step_tile_fwd")
+        if not infer:
+            ctx.save_for_backward(h, WT, WsT, AT, UcT, m, rz, c)
+        ctx.pb, ctx.first = pb, int(first)
+        LOOP_PATHS["fused"] += 1
+        return hout
+
+    @staticmethod
+    def backward(ctx, dhout):
+        L = _lib.lib()
+        h, WT, WsT, AT, UcT, m, rz, c = ctx.saved_tensors
+        pb, first = ctx.pb, ctx.first
+        dhout = dhout.contiguous()
+        N, d = h.shape
+        Wnat_p, Ws_p, A_p, Uc_p = pack_k4(WT.t()), pack_k4(WsT.t()), pack_k4(AT.t()), pack_k4(UcT.t())
+        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+        dh, gda = f(d), f(8 * d)
+        rh = None if first else f(d)
+        check(L.bmp_ggnn_loop_step_tile_bwd(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_tiles, d, first, ptr(pb.csrT_ptr),
+                                            ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Ws_p), ptr(A_p), ptr(Uc_p), ptr(dh),
+                                            ptr(gda), ptr(rh), stream()), "bmp_ggnn_loop_step_tile_bwd")
+        o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dWsT | dAT's h half; all column sums
+        o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
+        dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
+        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
+        return (dh, dWT, cs[:4 * d].reshape(4, d), o1[:, 4 * d:5 * d], cs[4 * d:5 * d], torch.cat((o1[:, 5 * d:], o2), dim=0), dUcT,
+                cs[5 * d:], None, None)
+
+
+def loop_step(h, WT, bE, WsT, bs, AT, UcT, b, first, pb, fused=True, state=None, state_w=None):
+    """One step of the self-loop GGNN; the weight layouts are LoopStepFn's.  The fused kernels where the tensors are on the GPU, the
+    width is supported and no molecule spans tiles; otherwise the existing operators, for any width that is a multiple of 8: the
+    message operator with its self connection (WsT, bs) and no activation, then the GRU operator.  ``state`` (with ``state_w`` =
+    GRU.kernel_weights_state(); training dropout, later calls): the GRU's own un-dropped state, apart from the dropped ``h`` -- the
+    separate-state GRU operator, composed at every width (AT, UcT and b are then not read).  Differentiable through autograd."""
+    d = h.shape[1]
+    if state is None and fused and h.is_cuda and whole_tiles_ok(pb) and loop_step_supported(d):
+        return LoopStepFn.apply(h, WT, bE, WsT, bs, AT, UcT, b, pb, first)
+    LOOP_PATHS["composed"] += 1
+    m = MsgFn.apply(h, WT, bE, WsT, bs, pb, ACT["identity"])
+    if state is not None:
+        return GRUStateFn.apply(h, m, state, *state_w, pb)
+    return GRUFn.apply(h, m, AT, UcT, b, pb, first)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # GGNN layer aggregators (models/ggnn.py:407-579): y = max_t h_t ('max-pool') or sum_s softmax_s(W x + b)_s h_s ('attn',
 # W = attn_dense_layer.W [T x T] over the LAYER axis), per row and channel of the T step outputs.
 # ---------------------------------------------------------------------------------------------------------

@@ -1,0 +1,207 @@
+"""The last two GRU-based GGNN encoders of the reference that a trainer reaches, with the reference's signatures:
+``models.ggnn_dev.GGNN`` (models/ggnn_dev.py:20-176; smiles_based_ddi.py:42, train_ddi_modify_eval3.py:49) as ``DevGGNN`` and
+``models.ggnn_dev_self_loop.GGNN`` (models/ggnn_dev_self_loop.py:20-145 = models/ggnn_dev_edge.py; train_binary.py:51,
+train_ddi_modify_eval2.py:43, train_ddi_modify_eval3.py:50) as ``SelfLoopGGNN``.
+
+Both keep models/ggnn.py's embedding, message (edge type the fastest axis of the 4d output), stateful GRU (first call after
+reset: no r gate, no U terms) and readout ``sum over ALL positions of sigmoid(i([h, h0])) * j(h)``.
+
+    DevGGNN       keeps every step's atom states and readout: ``get_atom_array(step=-1)`` and ``get_g_list()``
+                  (train_ddi_modify_eval3.py:116-138).  Without ``concat_hidden`` the call returns the SUM over all A padded
+                  positions of the last step's h (:165-168 compute the readout and then overwrite it) -- (mb, hidden_dim), not
+                  out_dim wide; i_layers / j_layers then receive gradient through get_g_list() only.
+    SelfLoopGGNN  adds ``message_self_loop_layers`` (one GraphLinear(d, d) per message layer) to the message:
+                  m = m + h W_s[l]^T + b_s[l], l = 0 if weight_tying else step (:96-97).  Padded positions have no bonds and one
+                  h, so m = W_s h + b_s there too and the one virtual pad row per molecule stays exact.  A step is
+                  ``Fn.loop_step``: one fused kernel per tile and direction at hidden_dim 64 / 128 on whole tiles
+                  (csrc/bmp_loop.hip), the composed operators otherwise.
+
+``dropout_rate`` (after every step): identity under ``eval()``; in training the step OUTPUT is dropped while the stateful GRU keeps
+its own un-dropped state (the separate-state GRU operator), and the zero-padded positions of a molecule are ONE row of the packed
+layout and share one mask, where the reference draws a mask per padded position -- same expectation, not the same random process
+(INTEGRATION.md).
+
+Parameter names follow the reference link tree (embed.W, message_layers.{i}.W/b, message_self_loop_layers.{i}.W/b,
+update_layer.{W_r,W_z,W,U_r,U_z,U}.W/b, i_layers.{k}.W/b, j_layers.{k}.W/b), so a snapshot maps key by key.
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import functional as Fn
+from .coarse import SegPoolFn
+from .ggnn import EmbedID, GRU, Linear, MAX_ATOMIC_NUM, NUM_EDGE_TYPE, PackedAtoms, _is_float_atoms, as_packed, message_kernel_weights
+
+
+class _DevBase(nn.Module):
+    """What the two files share: constructor checks, links, readout and the step loop (``_step`` is the subclass's)."""
+
+    NUM_EDGE_TYPE = NUM_EDGE_TYPE
+
+    def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
+        super().__init__()
+        if batch_normalization:     # (the files store the flag and never read it; refused like bmp.ggnn.GGNN's)
+            raise NotImplementedError("batch_normalization=True is not supported")
+        if not 0.0 <= dropout_rate < 1.0:
+            raise ValueError("dropout_rate must lie in [0, 1)")
+        if hidden_dim % 8:
+            raise ValueError("hidden_dim must be a multiple of 8 for the MFMA kernels")
+        if out_dim % 4:
+            raise ValueError("out_dim must be a multiple of 4")
+        self.out_dim, self.hidden_dim, self.n_layers = out_dim, hidden_dim, n_layers
+        self.concat_hidden, self.dropout_rate, self.weight_tying = concat_hidden, dropout_rate, weight_tying
+        self.batch_normalization = batch_normalization
+        self.n_readout_layer = n_layers if concat_hidden else 1
+        self.n_message_layer = 1 if weight_tying else n_layers
+        self.embed = EmbedID(out_size=hidden_dim, in_size=n_atom_types)
+        self.message_layers = nn.ModuleList([Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
+
+    def _make_update_and_readout(self):
+        self.update_layer = GRU(2 * self.hidden_dim, self.hidden_dim)
+        self.i_layers = nn.ModuleList([Linear(2 * self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
+        self.j_layers = nn.ModuleList([Linear(self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
+
+    def plannable(self) -> bool:
+        return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
+
+    def readout(self, h, h0, pb, step=0):
+        """i sees [h, h0], j sees h only -> j's h0 rows are zero in the kernel layout."""
+        i, j = self.i_layers[step if self.concat_hidden else 0], self.j_layers[step if self.concat_hidden else 0]
+        d = self.hidden_dim
+        WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
+        return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
+
+    def _steps(self, atom_array, adj):
+        """embed + the propagation steps: (pb, h0, [h after every step, dropout applied])."""
+        if _is_float_atoms(atom_array):
+            raise NotImplementedError("float atom features (embedding bypass, models/ggnn_dev.py:140-143, "
+                                      "models/ggnn_dev_self_loop.py:125-128) are not supported")
+        pb = as_packed(atom_array, adj, self.embed.W.device)
+        pb.check_atom_ids(self.embed.W.shape[0])
+        h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+        h0 = h
+        drop = self.dropout_rate != 0.0 and self.training
+        masks = getattr(self, "_dropout_masks", None) if drop else None      # tests inject the masks (one (n_rows, d) tensor per step)
+        if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
+            raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
+        ctx = dict(pb=pb, drop=drop, state=None, later=None, state_w=None, msgw={}, cache={})
+        hs = []
+        for step in range(self.n_layers):
+            s = self._step(h, step, ctx)
+            if drop:            # the stateful GRU keeps the un-dropped state; chainer's dropout: mask / (1 - ratio)
+                ctx["state"] = s
+                h = s * masks[step] if masks is not None else torch.nn.functional.dropout(s, p=self.dropout_rate, training=True)
+            else:
+                h = s
+            hs.append(h)
+        return pb, h0, hs
+
+    def _gru_weights(self, step, ctx):
+        if step == 0:
+            return self.update_layer.kernel_weights(first=True)
+        if ctx["later"] is None:
+            ctx["later"] = self.update_layer.kernel_weights(first=False)
+        return ctx["later"]
+
+    def _state_weights(self, ctx):
+        if ctx["state_w"] is None:
+            ctx["state_w"] = self.update_layer.kernel_weights_state()
+        return ctx["state_w"]
+
+    def _step(self, h, step, ctx):
+        raise NotImplementedError
+
+
+class DevGGNN(_DevBase):
+    """models/ggnn_dev.py:20-176."""
+
+    fused = True                # use the fused per-tile step kernel where the width allows, as bmp.ggnn.GGNN
+
+    def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
+                 batch_normalization=False, weight_tying=True, output_atoms=True):
+        super().__init__(out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying)
+        self.output_atoms = output_atoms
+        self._make_update_and_readout()
+        self.atoms_list, self.g_vec_list = [], []
+
+    def _step(self, h, step, ctx):
+        """bmp.ggnn.GGNN.forward's step, without the planned path."""
+        pb, li = ctx["pb"], (0 if self.weight_tying else step)
+        if li not in ctx["msgw"]:
+            ctx["msgw"][li] = message_kernel_weights(self.message_layers[li])
+        WT, bE = ctx["msgw"][li]
+        AT, UcT, b = self._gru_weights(step, ctx)
+        if self.fused and Fn.step_supported(self.hidden_dim) and not ctx["drop"] and not pb.oversized:
+            return Fn.GGNNStepFn.apply(h, WT, bE, AT, UcT, b, pb, step == 0, ctx["cache"])
+        m = Fn.MsgFn.apply(h, WT, bE, None, None, pb, Fn.ACT["identity"])
+        if ctx["state"] is not None:
+            return Fn.GRUStateFn.apply(h, m, ctx["state"], *self._state_weights(ctx), pb)
+        return Fn.GRUFn.apply(h, m, AT, UcT, b, pb, step == 0)
+
+    def forward(self, atom_array, adj=None):
+        """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
+        ignored).  Returns (n_mols, hidden_dim): the sum of the last step's atom states over ALL A positions (:165-168) --
+        with concat_hidden (n_mols, n_layers * out_dim), the concatenated readouts."""
+        self.atoms_list, self.g_vec_list = [], []               # :137-138
+        pb, h0, hs = self._steps(atom_array, adj)
+        side = 0 if pb.dense_map is not None else None
+        self.atoms_list = [PackedAtoms(h, pb, side) for h in hs]
+        self.g_vec_list = [self.readout(h, h0, pb, t) for t, h in enumerate(hs)]       # :159-160
+        if self.concat_hidden:
+            return torch.cat(self.g_vec_list, dim=1)            # (:153-155 compute the same readouts a second time)
+        h = hs[-1]
+        ones = torch.ones(h.shape[0], 1, dtype=h.dtype, device=h.device)
+        return SegPoolFn.apply(ones, h, pb.row_w, pb.mol_row0, pb.mol_nrows)           # the pad row counts with its multiplicity
+
+    def graph_vector_dim(self) -> int:
+        """Width of what the call returns per molecule (the pair predictor sizes its link predictor by it)."""
+        return self.n_layers * self.out_dim if self.concat_hidden else self.hidden_dim
+
+    def get_atom_array(self, step=-1):
+        """:170-172.  Returns that step's PackedAtoms; ``.dense()`` gives (mb, A, hidden_dim)."""
+        assert len(self.atoms_list) > 0
+        return self.atoms_list[step]
+
+    def get_g_list(self):
+        """:174-176: the T readouts readout(h_t, h0, t), each (n_mols, out_dim)."""
+        assert len(self.g_vec_list) > 0
+        return self.g_vec_list
+
+
+class SelfLoopGGNN(_DevBase):
+    """models/ggnn_dev_self_loop.py:20-145 = models/ggnn_dev_edge.py."""
+
+    _fused = True               # private switch: False takes the composed operators at every width
+
+    def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
+                 batch_normalization=False, weight_tying=True):
+        super().__init__(out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying)
+        self.message_self_loop_layers = nn.ModuleList([Linear(hidden_dim, hidden_dim) for _ in range(self.n_message_layer)])
+        self._make_update_and_readout()
+        self.atoms = None
+
+    def _step(self, h, step, ctx):
+        pb, li = ctx["pb"], (0 if self.weight_tying else step)
+        if li not in ctx["msgw"]:
+            sl = self.message_self_loop_layers[li]
+            ctx["msgw"][li] = message_kernel_weights(self.message_layers[li]) + (sl.W.t().contiguous(), sl.b)
+        AT, UcT, b = self._gru_weights(step, ctx)
+        if ctx["state"] is not None:
+            return Fn.loop_step(h, *ctx["msgw"][li], AT, UcT, b, False, pb, False, ctx["state"], self._state_weights(ctx))
+        return Fn.loop_step(h, *ctx["msgw"][li], AT, UcT, b, step == 0, pb, self._fused and not ctx["drop"])
+
+    def forward(self, atom_array, adj=None):
+        """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
+        ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
+        pb, h0, hs = self._steps(atom_array, adj)
+        self.atoms = PackedAtoms(hs[-1], pb, 0 if pb.dense_map is not None else None)
+        if self.concat_hidden:
+            return torch.cat([self.readout(h, h0, pb, t) for t, h in enumerate(hs)], dim=1)
+        return self.readout(hs[-1], h0, pb, 0)
+
+    def get_atom_array(self):
+        """Not in the file: the last step's atom states, so that the encoder composes with every co-attention (as
+        models/ggnn_att.py:662-664 does for the GRU form)."""
+        assert self.atoms is not None
+        return self.atoms

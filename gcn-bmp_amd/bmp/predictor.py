@@ -31,6 +31,8 @@ class GraphConvPredictorForPair(nn.Module):
         if attn is None and getattr(graph_conv, "concat_hidden", False):
             # models/ggnn.py:646-647; GIN concatenates one readout per layer that RAN (models/gin.py:215-223: n_concat)
             fp = fp * getattr(graph_conv, "n_concat", graph_conv.n_layers)
+        if attn is None and callable(getattr(graph_conv, "graph_vector_dim", None)):
+            fp = graph_conv.graph_vector_dim()           # bmp.ggnn_dev.DevGGNN: hidden_dim wide without concat_hidden
         if fp is not None and callable(getattr(mlp, "materialize_input", None)):
             mlp.materialize_input(int(fp))
 
@@ -168,6 +170,10 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
         from .ggnn_gate import FuseGGNN, GateGGNN
         cls = FuseGGNN if encoder == "ggnn-fuse" else GateGGNN
         enc = cls(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
+    elif encoder in ("ggnn-dev", "ggnn-self-loop"):  # smiles_based_ddi.py:42, train_ddi_modify_eval3.py:49-50: chosen by import there
+        from .ggnn_dev import DevGGNN, SelfLoopGGNN
+        cls = DevGGNN if encoder == "ggnn-dev" else SelfLoopGGNN
+        enc = cls(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
     else:
         raise ValueError('[ERROR] Invalid graph embedding encoder.')
     a = None
@@ -205,6 +211,9 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
         a = NeuralCoattention(hidden_dim=hidden_dim, out_dim=out_dim, activation="tanh")
     elif attn is not None:
         raise ValueError('[ERROR] Invalid Co-Attention Method.')
-    # BiMPM hands over 3 * head columns; without a co-attention GIN hands over one readout per layer that ran
+    # BiMPM hands over 3 * head columns; without a co-attention GIN hands over one readout per layer that ran and the
+    # ggnn_dev encoder the sum of its atom states (hidden_dim wide)
     fp_dim = getattr(a, "out_dim", out_dim) if a is not None else out_dim * getattr(enc, "n_concat", 1)
+    if a is None and callable(getattr(enc, "graph_vector_dim", None)):
+        fp_dim = enc.graph_vector_dim()
     return GraphConvPredictorForPair(enc, a, build_link_predictor(sim_method, fp_dim, class_num, mlp_hidden))

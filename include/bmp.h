@@ -234,6 +234,37 @@ int bmp_ggnn_gate_step_tile_bwd(int kind, const float* dhout, const float* h, co
                                 int n_tiles, int d, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
                                 const float* Wnat_p, const float* Unat_p, float* dh, float* gda, bmp_stream_t stream);
 
+/* ---- GGNN step with a per-atom self loop in the message -- models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py
+ * (csrc/bmp_loop.hip) ----
+ * The GRU step of bmp_ggnn_step_* with a fifth message operand: m = sum_e (agg_e . W_e + wdeg_e b_e) + h . W_s^T + b_s, then the
+ * GRU on [h, m] with the state folded into the h-part; first != 0 selects the first call after reset (no r gate, no U term:
+ * out = z * c).  `first` is an argument here and a template parameter of the kernels: the entry picks the instance.
+ * One kernel per direction, one workgroup per 128-row tile, d with bmp_ggnn_loop_step_supported (64 or 128), exact-f32 MFMA; whole
+ * tiles whose molecules never straddle a tile (no tile table).  N = 128 n_tiles.
+ * fwd: WTp [4d x d], bE [4 x d], ATp [2d x 3d] (rows [h; m], columns [r | z | c]), UcTp [d x d] and b [3d] as for
+ *      bmp_ggnn_step_fwd; WsTp [d x d] = W_s^T (K-major), K4-packed; bs [d].  Saves m [N x d], rz [N x 2d] and c [N x d] (all three
+ *      may be NULL together: forward-only evaluation) and writes hout [N x d].  first != 0: the r half of rz is not written and
+ *      UcTp is not read.
+ * bwd: Wnat_p [d x 4d], A_p [3d x 2d] and Uc_p [d x d] as for bmp_ggnn_step_bwd; Ws_p [d x d] = W_s in the reference layout
+ *      [out x in], K4-packed.  Reads dhout, h, rz, c (m is the weight-gradient call's operand only).  Writes dh [N x d],
+ *      gda [N x 8d] = [G_0 .. G_3 | dm | da_r | da_z | da_c] -- G_e the transposed-CSR gather of dm over the bonds of type e -- and,
+ *      for later calls, rh [N x d] = r * h.  first != 0: the da_r block is written as zeros (a full-width weight-gradient call
+ *      is legal), rh is not written and may be NULL, Uc_p is not read.  A row that enters with a zero dhout leaves with zero dh
+ *      and gda rows: no bias-like constant enters the backward.
+ * Weight gradients: calls of bmp_linear_wgrad (deterministic, no atomics) -- X = h, dY = gda over all 8d columns gives dWT
+ * ([k][e d + c]), dWsT, the h half of dAT and the column sums (dbE | dbs | db); X = m, dY = gda + 5d (ldy = 8d, 3d columns) gives
+ * the m half of dAT; later calls only: X = rh, dY = gda + 7d (d columns, no bias) gives dUcT.
+ * No allocation, no host sync; every row array 16-byte aligned. */
+int bmp_ggnn_loop_step_supported(int d);
+int bmp_ggnn_loop_step_tile_fwd(const float* h, int n_tiles, int d, int first, const int* csr_ptr, const int* csr_col,
+                                const float* csr_val, const float* WTp, const float* bE, const float* WsTp, const float* bs,
+                                const float* ATp, const float* UcTp, const float* b, float* m, float* rz, float* c, float* hout,
+                                bmp_stream_t stream);
+int bmp_ggnn_loop_step_tile_bwd(const float* dhout, const float* h, const float* rz, const float* c, int n_tiles, int d, int first,
+                                const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* Wnat_p,
+                                const float* Ws_p, const float* A_p, const float* Uc_p, float* dh, float* gda, float* rh,
+                                bmp_stream_t stream);
+
 /* ---- Neural-fingerprint encoder -- models/models/nfp.py (csrc/bmp_nfp.hip) ----
  * ONE adjacency: every bond counts once whatever its type (csr_col >> 2 is the source row), plus a self loop of weight
  * self_w [N] on the rows that have one (1 on real atoms, 0 on pad and dead rows).  deg_class [N] in 0..7: k when the COLUMN
