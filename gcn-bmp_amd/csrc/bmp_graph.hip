@@ -20,10 +20,9 @@ __global__ __launch_bounds__(256) void k_embed_fwd(const int* __restrict__ ids, 
 }
 
 // dW[id, :] = sum_{rows with ids[row]==id} dout[row, :], in two deterministic passes.  Pass 1: each workgroup
-// accumulates its 128-row chunk in an LDS copy of the table (V x d floats) and writes the table rows it touched,
-// plus a touched flag per id, to its own slab.  Pass 2: one workgroup per id sums that row over the slabs in a
-// fixed order.  (Most rows are carbon or padding: flushing the LDS tables with global float atomics sent ~450
-// memory-side atomic requests to each of a handful of 64-byte lines and took 45 of the kernel's 60 us.)
+// accumulates its 128-row chunk in an LDS copy of the table (V x d floats), a thread per column, and writes the table
+// rows it touched, plus a touched flag per id, to its own slab.  Pass 2: one workgroup per id sums that row over the
+// slabs in a fixed order.  (The path of row counts that are no multiple of 32 only: packed batches take the one-hot GEMM.)
 __global__ __launch_bounds__(256) void k_embed_bwd(const int* __restrict__ ids, const float* __restrict__ dout, int N, int d,
                                                    int V, int rows_per_block, float* __restrict__ slab, int* __restrict__ flags) {
     extern __shared__ float tab[];                // V*d floats + V flags
@@ -33,29 +32,17 @@ __global__ __launch_bounds__(256) void k_embed_bwd(const int* __restrict__ ids, 
     __syncthreads();
     const int r0 = blockIdx.x * rows_per_block;
     const int r1 = (r0 + rows_per_block) < N ? (r0 + rows_per_block) : N;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    // eight rows of a wave in flight at a time
-    for (int base = r0 + wave; base < r1; base += 32) {
-        int id8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int row = base + 4 * u;
-            id8[u] = row < r1 ? ids[row] : -1;
-            if (id8[u] >= V) id8[u] = -1;          // out-of-range ids contribute nothing (and touch no LDS)
+    // one thread per column walks the chunk's rows in order: every table entry has ONE writer and a fixed summation order (bitwise
+    // reproducible, as the header promises; the waves' LDS float atomics this replaces met at an entry in whatever order the
+    // waves were scheduled).  Out-of-range ids contribute nothing and touch no LDS.
+    for (int c = threadIdx.x; c < d; c += 256)
+        for (int row = r0; row < r1; ++row) {
+            const int id = ids[row];
+            if ((unsigned)id < (unsigned)V) tab[(size_t)id * d + c] += dout[(size_t)row * d + c];
         }
-        for (int c = lane; c < d; c += 64) {
-            float v8[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v8[u] = id8[u] >= 0 ? dout[(size_t)(base + 4 * u) * d + c] : 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (id8[u] >= 0) atomicAdd(&tab[(size_t)id8[u] * d + c], v8[u]);
-        }
-        if (lane == 0) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (id8[u] >= 0) touched[id8[u]] = 1;
-        }
+    for (int row = r0 + threadIdx.x; row < r1; row += 256) {
+        const int id = ids[row];
+        if ((unsigned)id < (unsigned)V) touched[id] = 1;
     }
     __syncthreads();
     float* my = slab + (size_t)blockIdx.x * V * d;
