@@ -1331,6 +1331,104 @@ def loop_step(h, WT, bE, WsT, bs, AT, UcT, b, first, pb, fused=True, state=None,
 
 
 # ---------------------------------------------------------------------------------------------------------
+# GGNN step with the edge-network message (EdgeNetwork, models/ggnn.py:657-720, behind GGNN.update's 'edge_network' branch;
+# csrc/bmp_edge.hip): m = sum_e agg_e . W_e^T + S . B^T, S = the molecule's row_w-weighted sum of h, no bias.
+# ---------------------------------------------------------------------------------------------------------
+EDGE_PATHS = {"fused": 0, "composed": 0}         # forward calls per form
+
+
+def edge_step_supported(d: int) -> bool:
+    return bool(_lib.lib().bmp_ggnn_edge_step_supported(int(d)))
+
+
+def _row_mol(pb):
+    """The molecule of every row (-1: none): the batch's own array, or one made from its segments and kept with the batch."""
+    if pb.row_mol is not None:
+        return pb.row_mol
+    if "edge_row_mol" not in pb._cache:
+        n = pb.mol_nrows.long()
+        mol = torch.repeat_interleave(torch.arange(pb.n_mols, device=pb.device, dtype=torch.int32), n)
+        rows = torch.repeat_interleave(pb.mol_row0.long() - (torch.cumsum(n, 0) - n), n) + torch.arange(mol.numel(), device=pb.device)
+        pb._cache["edge_row_mol"] = torch.full((pb.n_rows,), -1, dtype=torch.int32, device=pb.device).index_put_((rows,), mol)
+    return pb._cache["edge_row_mol"]
+
+
+class EdgeStepFn(Function):
+    """One propagation step -- the edge-network message, then the GRU on [h, m] -- as ONE fused kernel per tile and direction.
+    WT [4d x d] (row e d + q, column p = W_e[p, q]), AT [2d x 3d], UcT [d x d], b [3d]: as GGNNStepFn takes them; BT [d x d] = B^T
+    (K-major).  d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes go through ``edge_step``."""
+
+    @staticmethod
+    def forward(ctx, h, WT, BT, AT, UcT, b, pb, first):
+        L = _lib.lib()
+        require_rows(h, "edge step: h")
+        _check_pb(pb, h)
+        N, d = h.shape
+        if tuple(WT.shape) != (4 * d, d) or tuple(BT.shape) != (d, d) or tuple(AT.shape) != (2 * d, 3 * d) \
+                or tuple(UcT.shape) != (d, d) or tuple(b.shape) != (3 * d,):
+            raise ValueError("edge step: weight shapes do not match h")
+        if not (whole_tiles_ok(pb) and edge_step_supported(d)):
+            raise ValueError("edge step: the fused kernels take d in {64, 128} on whole tiles; use edge_step()")
+        b = b.contiguous()
+        WTp, BTp, ATp, UcTp = pack_k4(WT), pack_k4(BT), pack_k4(AT), pack_k4(UcT)
+        row_mol = _row_mol(pb)
+        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+        infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
+        m, rz, c, hout = (None, None, None, f(d)) if infer else (f(d), f(2 * d), f(d), f(d))
+        check(L.bmp_ggnn_edge_step_tile_fwd(ptr(h), pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                                            ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), pb.n_mols, ptr(WTp),
+                                            ptr(BTp), ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c), ptr(hout), stream()),
+              "bmp_ggnn_edge_step_tile_fwd")
+        if not infer:
+            ctx.save_for_backward(h, WT, BT, AT, UcT, m, rz, c, row_mol)
+        ctx.pb, ctx.first = pb, int(first)
+        EDGE_PATHS["fused"] += 1
+        return hout
+
+    @staticmethod
+    def backward(ctx, dhout):
+        L = _lib.lib()
+        h, WT, BT, AT, UcT, m, rz, c, row_mol = ctx.saved_tensors
+        pb, first = ctx.pb, ctx.first
+        dhout = dhout.contiguous()
+        N, d = h.shape
+        Wnat_p, B_p, A_p, Uc_p = pack_k4(WT.t()), pack_k4(BT.t()), pack_k4(AT.t()), pack_k4(UcT.t())
+        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+        dh, gda = f(d), f(8 * d)
+        rh = None if first else f(d)
+        check(L.bmp_ggnn_edge_step_tile_bwd(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_tiles, d, first, ptr(pb.csrT_ptr),
+                                            ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0),
+                                            ptr(pb.mol_nrows), pb.n_mols, ptr(Wnat_p), ptr(B_p), ptr(A_p), ptr(Uc_p), ptr(dh), ptr(gda),
+                                            ptr(rh), stream()), "bmp_ggnn_edge_step_tile_bwd")
+        o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dBT | dAT's h half; cs: db in its last 3d
+        o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
+        dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
+        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
+        return dh, dWT, o1[:, 4 * d:5 * d], torch.cat((o1[:, 5 * d:], o2), dim=0), dUcT, cs[5 * d:], None, None
+
+
+def edge_step(h, WT, BT, AT, UcT, b, first, pb, fused=True, state=None, state_w=None):
+    """One step of the GGNN with the edge-network message; the weight layouts are EdgeStepFn's.  The fused kernels where the
+    tensors are on the GPU, the width is supported and the batch is whole tiles; otherwise the existing operators, for any width
+    that is a multiple of 8: the message operator with a zero per-edge bias, plus the row broadcast of (the molecules' row_w-weighted
+    segment sums of h) . BT -- an [n_mols x d] . [d x d] product, 1/27 of one message block, left to torch.matmul -- then the GRU
+    operator.  ``state`` (with ``state_w`` = GRU.kernel_weights_state(); training dropout, later calls): the GRU's own un-dropped
+    state, apart from the dropped ``h`` -- the separate-state GRU operator, composed at every width (AT, UcT and b are then not
+    read).  Differentiable through autograd."""
+    d = h.shape[1]
+    if state is None and fused and h.is_cuda and whole_tiles_ok(pb) and edge_step_supported(d):
+        return EdgeStepFn.apply(h, WT, BT, AT, UcT, b, pb, first)
+    from .coarse import RowBcastFn, SegPoolFn
+    EDGE_PATHS["composed"] += 1
+    m = MsgFn.apply(h, WT, torch.zeros(4, d, dtype=h.dtype, device=h.device), None, None, pb, ACT["identity"])
+    S = SegPoolFn.apply(torch.ones(h.shape[0], 1, dtype=h.dtype, device=h.device), h, pb.row_w, pb.mol_row0, pb.mol_nrows)
+    m = m + RowBcastFn.apply(torch.matmul(S, BT), _row_mol(pb), pb.mol_row0, pb.mol_nrows)
+    if state is not None:
+        return GRUStateFn.apply(h, m, state, *state_w, pb)
+    return GRUFn.apply(h, m, AT, UcT, b, pb, first)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # GGNN layer aggregators (models/ggnn.py:407-579): y = max_t h_t ('max-pool') or sum_s softmax_s(W x + b)_s h_s ('attn',
 # W = attn_dense_layer.W [T x T] over the LAYER axis), per row and channel of the T step outputs.
 # ---------------------------------------------------------------------------------------------------------

@@ -4,14 +4,16 @@ Mirrors ``models.ggnn.GGNN`` (models/ggnn.py:19-654) and ``models.ggnn_att.GGNN`
 (models/ggnn_att.py:39-664, which adds ``self.atoms`` / ``get_atom_array()``) on the default
 path: message_function='matrix_multiply', readout_function='graph_level', no attention, no context BiLSTM, no batch
 normalisation, plus the closed-form layer aggregators 'concat', 'max-pool' and 'attn' (models/ggnn.py:154-213, 407-579:
-the T step outputs of an atom, combined per channel, go to the readout in the last step's place).  Any other option
-raises NotImplementedError (they are research ablations outside SURVEY.md section 8).
+the T step outputs of an atom, combined per channel, go to the readout in the last step's place) and
+message_function='edge_network' (``EdgeNetwork`` below).  Any other option raises NotImplementedError (they are research
+ablations outside SURVEY.md section 8).
 
 ``dropout_rate`` (models/ggnn.py:626-627): identity under ``eval()``; in training the zero-padded positions of a molecule
 are ONE row of the packed layout and share one mask, where the reference draws a mask per padded position -- same
 expectation, not the same random process; the float-feature input form keeps every position a row of its own.
 
-Parameter names and shapes follow the reference link tree (embed.W, message_layers.{i}.W/b,
+Parameter names and shapes follow the reference link tree (embed.W, message_layers.{i}.W/b -- with 'edge_network'
+message_layers.{i}.output_layer.W/b and message_layers.{i}.hidden_layers.0.W/b --,
 update_layer.{W_r,W_z,W,U_r,U_z,U}.W/b, i_layers.{k}.W/b, j_layers.{k}.W/b) so a Chainer
 snapshot maps key by key.
 """
@@ -108,6 +110,42 @@ def message_kernel_weights(lin: Linear):
     WT = lin.W.view(d_out, NUM_EDGE_TYPE, d_in).permute(1, 2, 0).reshape(NUM_EDGE_TYPE * d_in, d_out)
     bE = lin.b.view(d_out, NUM_EDGE_TYPE).t() if lin.b is not None else torch.zeros(NUM_EDGE_TYPE, d_out, device=lin.W.device)
     return WT.contiguous(), bE.contiguous()
+
+
+class EdgeNetwork(nn.Module):
+    """Parameters of the reference's EdgeNetwork (models/ggnn.py:657-720) as GGNN builds it (:95: no hidden layers):
+    ``output_layer`` = Linear(4, d * d) maps the adjacency vector adj[b, :, i, j] of an atom pair to a d x d matrix E_ij (entry
+    [p, q] at index p d + q), and m_i = sum over ALL A positions j of E_ij h_j (:702-713; the message bias of :715-717 is a
+    constant zero).  The map is affine, so with W_e[p, q] = output_layer.W[p d + q, e] and B[p, q] = output_layer.b[p d + q]
+
+        m_i = sum_e W_e . (sum_j adj[e, i, j] h_j) + B . S,      S = the sum of h over all A positions of the molecule
+
+    exactly, for any adjacency values: the typed neighbour sums of the GGNN message without its per-edge bias, plus one
+    vector per molecule.  ``hidden_layers.0`` = Linear(4, edge_hidden_dim) is built by the reference and never called: it is
+    kept for the snapshot's key layout and never read, so ``edge_hidden_dim`` has no effect.  The reference's ``bias_add_layer``
+    (links.Bias without a shape) never gets a parameter and has no counterpart."""
+
+    def __init__(self, in_dim: int, hidden_dim: int, node_dim: int):
+        super().__init__()
+        self.hidden_layers = nn.ModuleList([Linear(in_dim, hidden_dim)])
+        # Never read, so never given a gradient: Chainer's optimizers skip such parameters, gradient hooks included
+        # (WeightDecay would otherwise shrink them).  requires_grad = False keeps them out of FlatAdam the same way.
+        for p in self.hidden_layers.parameters():
+            p.requires_grad_(False)
+        self.output_layer = Linear(in_dim, node_dim * node_dim)
+        self.in_dim, self.hidden_dim, self.node_dim = in_dim, hidden_dim, node_dim
+
+    def kernel_weights(self):
+        """(WT [4d x d] with row e d + q, column p = W_e[p, q]; BT [d x d] = B^T): the layouts of Fn.edge_step."""
+        d, lin = self.node_dim, self.output_layer
+        WT = lin.W.view(d, d, self.in_dim).permute(2, 1, 0).reshape(self.in_dim * d, d)
+        return WT.contiguous(), lin.b.view(d, d).t().contiguous()
+
+
+EDGE_NETWORK_LAYOUT_REASON = (
+    "with message_function='edge_network' every atom's message holds the sum of the atom states over ALL A padded positions of "
+    "its molecule, so a molecule's states depend on the padded atom count A of its batch side: one pad row per tile (the encoder "
+    "layout) or one encoding per distinct molecule (dedup) is not valid for it; use the per-instance batch form")
 
 
 class PackedAtoms:
@@ -253,9 +291,7 @@ class GGNN(nn.Module):
         if not 0.0 <= dropout_rate < 1.0:
             raise ValueError("dropout_rate must lie in [0, 1)")
         self.dropout_rate = dropout_rate        # models/ggnn.py:626-627; see forward()
-        if message_function != 'matrix_multiply':
-            if message_function == 'edge_network':
-                raise NotImplementedError("message_function='edge_network' is not supported")
+        if message_function not in ('matrix_multiply', 'edge_network'):
             raise ValueError('There is no such message function named {}'.format(message_function))  # models/ggnn.py:250
         if readout_function != 'graph_level':
             raise NotImplementedError("readout_function='set2vec' is not supported")
@@ -267,9 +303,14 @@ class GGNN(nn.Module):
         self.concat_hidden, self.weight_tying = concat_hidden, weight_tying
         self.n_readout_layer = n_layers if concat_hidden else 1
         self.n_message_layer = 1 if weight_tying else n_layers
+        self.message_function, self.edge_hidden_dim = message_function, edge_hidden_dim
         self.embed = EmbedID(out_size=hidden_dim, in_size=n_atom_types)
-        self.message_layers = nn.ModuleList(
-            [Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
+        if message_function == 'edge_network':          # models/ggnn.py:92-97
+            self.message_layers = nn.ModuleList(
+                [EdgeNetwork(NUM_EDGE_TYPE, edge_hidden_dim, hidden_dim) for _ in range(self.n_message_layer)])
+        else:
+            self.message_layers = nn.ModuleList(
+                [Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
         self.update_layer = GRU(2 * hidden_dim, hidden_dim)
         # construct_layer_aggregator (models/ggnn.py:168-213): 'concat' reads the T step outputs side by side
         ro_dim = n_layers * hidden_dim if self.layer_aggregator == 'concat' else hidden_dim
@@ -296,6 +337,8 @@ class GGNN(nn.Module):
 
     # ---- layout plan protocol (bmp/plan.py): the weight-layout code above as pure functions of the parameters ----
     def plannable(self) -> bool:
+        if self.message_function == 'edge_network':     # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
+            return False
         return self.fused and not self.concat_hidden and self.dropout_rate == 0.0 and self.layer_aggregator != 'concat'
 
     def aggregate(self, hs, h0, fast=None):
@@ -492,6 +535,8 @@ class GGNN(nn.Module):
         entry the pair predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the
         per-instance rows (``readout_rows``).  With a layer aggregator ``h`` is the aggregate of the step outputs (and, for
         'concat', h0 its T-fold repetition): per row and channel, so it commutes with the copy to the instance rows."""
+        if self.message_function == 'edge_network':
+            raise NotImplementedError("encode_rows: " + EDGE_NETWORK_LAYOUT_REASON)
         if self.concat_hidden or (self.dropout_rate != 0.0 and self.training):
             raise NotImplementedError("encode_rows: concat_hidden / training dropout take the per-instance batch form")
         fast = getattr(self, "_fast", None)
@@ -557,7 +602,8 @@ class GGNN(nn.Module):
         h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id) if h_in is None else h_in      # :603
         h0 = h                                                          # :612
         later = None
-        fused = self.fused and self._plan_fused() and not drop and not big
+        edge = self.message_function == 'edge_network'
+        fused = self.fused and self._plan_fused() and not drop and not big and not edge
         state, state_w = None, None           # dropout: the GRU's own (un-dropped) state and its unfolded weights
         masks = getattr(self, "_dropout_masks", None)      # tests inject the masks (one (n_rows, d) tensor per step)
         g_list, hs = [], []
@@ -565,8 +611,8 @@ class GGNN(nn.Module):
         msgw, cache = {}, {}          # per-call: kernel-layout weights of each layer, packed copies
         for step in range(self.n_layers):                               # :616
             li = 0 if self.weight_tying else step                       # :220
-            if li not in msgw:
-                msgw[li] = message_kernel_weights(self.message_layers[li])
+            if li not in msgw:          # (edge network: WT and, in bE's place, B^T -- EdgeNetwork.kernel_weights)
+                msgw[li] = self.message_layers[li].kernel_weights() if edge else message_kernel_weights(self.message_layers[li])
             WT, bE = msgw[li]
             if step == 0:
                 AT, UcT, b = self.update_layer.kernel_weights(first=True)
@@ -576,13 +622,18 @@ class GGNN(nn.Module):
                 AT, UcT, b = later
             if fused:       # message + GRU in one kernel per tile, atom states resident in LDS
                 h = Fn.GGNNStepFn.apply(h, WT, bE, AT, UcT, b, pb, step == 0, cache)
+            elif edge and not drop:     # :245-248: one fused kernel per tile and direction at 64 / 128, composed operators otherwise
+                h = Fn.edge_step(h, WT, bE, AT, UcT, b, step == 0, pb, self.fused)
             elif drop:
-                m = Fn.MsgFn.apply(h, WT, bE, None, None, pb, Fn.ACT["identity"])
-                if state is None:
+                if state is not None and state_w is None:
+                    state_w = self.update_layer.kernel_weights_state()
+                if edge:
+                    state = Fn.edge_step(h, WT, bE, AT, UcT, b, state is None, pb, False, state, state_w)
+                elif state is None:
+                    m = Fn.MsgFn.apply(h, WT, bE, None, None, pb, Fn.ACT["identity"])
                     state = Fn.GRUFn.apply(h, m, AT, UcT, b, pb, True)             # first call after reset: no state yet
                 else:
-                    if state_w is None:
-                        state_w = self.update_layer.kernel_weights_state()
+                    m = Fn.MsgFn.apply(h, WT, bE, None, None, pb, Fn.ACT["identity"])
                     state = Fn.GRUStateFn.apply(h, m, state, *state_w, pb)
                 if masks is not None:
                     h = state * masks[step]

@@ -155,6 +155,8 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
     encoder's (the trainer builds it with 0.5); the other encoders do not read it."""
     if encoder == "ggnn":
         enc = GGNN(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
+    elif encoder == "ggnn-edge":                     # ggnn_hole.py:202, train_ggnn_hole_with_gwm.py:276: --message-function edge_network
+        enc = GGNN(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying, message_function='edge_network')
     elif encoder == "relgcn":
         from .relgcn import RelGCN
         enc = RelGCN(out_channels=out_dim, ch_list=[hidden_dim] * (n_layers + 1), scale_adj=True)

@@ -198,6 +198,19 @@ class PairBatches:
         self.B, self.shuffle, self.seed, self.layout, self.dedup = int(batch_size), shuffle, seed, layout, dedup
         self.rank, self.world, self.share, self.epoch = rank, world, share, 0
 
+    def check_encoder(self, model) -> None:
+        """Refuse a layout the model's encoder cannot take: with message_function='edge_network' a molecule's atom states depend
+        on the padded atom count of its batch side, which the encoder layout and ``dedup`` give up (``fit`` asks before the first
+        batch)."""
+        enc = getattr(model, "graph_conv", model)
+        if getattr(enc, "message_function", None) != "edge_network":
+            return
+        if self.layout == "encoder":
+            from .ggnn import EDGE_NETWORK_LAYOUT_REASON
+            raise NotImplementedError(f"PairBatches(layout='encoder', dedup={self.dedup}): " + EDGE_NETWORK_LAYOUT_REASON)
+        if self.layout == "static":
+            raise NotImplementedError("PairBatches(layout='static'): the recorded step is not built for message_function='edge_network'")
+
     def __len__(self) -> int:
         g = self.B * self.world
         full, rem = divmod(len(self.lab), g)
@@ -239,6 +252,8 @@ def fit(model, opt, train_batches: Sequence, valid_batches: Sequence = (), epoch
         report: Optional[Callable[[Dict[str, float]], None]] = None) -> List[Dict[str, float]]:
     """One StandardUpdater loop (train_binary.py:551-553) with bmp.dp.FlatAdam ``opt``: per batch forward, loss,
     backward, one gradient all-reduce, Adam; per epoch the evaluators, the alpha shift and the stop trigger."""
+    if callable(getattr(train_batches, "check_encoder", None)):
+        train_batches.check_encoder(model)
     logs: List[Dict[str, float]] = []
     t0 = time.time()
     stepper = None

@@ -1,5 +1,5 @@
-// Whole-tile machinery shared by the fused per-tile kernels of the GIN, NFP, gated-GGNN and self-loop GGNN encoders (bmp_gin.hip,
-// bmp_nfp.hip, bmp_gate.hip, bmp_loop.hip): one workgroup of 512 threads (8 waves) per 128-row tile, d in {64, 128}, exact-f32 MFMA 32x32x2, two
+// Whole-tile machinery shared by the fused per-tile kernels of the GIN, NFP, gated-GGNN, self-loop and edge-network GGNN encoders
+// (bmp_gin.hip, bmp_nfp.hip, bmp_gate.hip, bmp_loop.hip, bmp_edge.hip): one workgroup of 512 threads (8 waves) per 128-row tile, d in {64, 128}, exact-f32 MFMA 32x32x2, two
 // [128][d + 4] tiles in LDS used in turn; wave w owns the 32-row block w >> 1 of the operand tile and the column half w & 1 of
 // the product.
 // Weights are K4-packed ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.

@@ -265,6 +265,37 @@ int bmp_ggnn_loop_step_tile_bwd(const float* dhout, const float* h, const float*
                                 const float* Ws_p, const float* A_p, const float* Uc_p, float* dh, float* gda, float* rh,
                                 bmp_stream_t stream);
 
+/* ---- GGNN step with the edge-network message -- EdgeNetwork, models/ggnn.py:657-720, behind GGNN(message_function=
+ * 'edge_network') (csrc/bmp_edge.hip) ----
+ * The network has no hidden layers (models/ggnn.py:95) and is affine in the adjacency vector of an atom pair: with
+ * W_e[p, q] = output_layer.W[p d + q, e] and B[p, q] = output_layer.b[p d + q],
+ *   m_i = sum_e W_e . agg_e(i) + B . S,   S = the row_w-weighted sum of h over the rows of the atom's molecule (all A padded
+ *   positions: the virtual pad row counts A - n times), no bias; then the GRU on [h, m] as for bmp_ggnn_loop_step_*.
+ * One kernel per direction, one workgroup per 128-row tile, d with bmp_ggnn_edge_step_supported (64 or 128), exact-f32 MFMA; whole
+ * tiles whose molecules never straddle a tile.  `first` is an argument here and a template parameter of the kernels.
+ * row_w [N], row_mol [N] (-1: a row of no molecule, whose S is zero), mol_row0 / mol_nrows [n_mols]: the batch's segments.
+ * fwd: WTp [4d x d] (row e d + q, column p = W_e[p, q]), ATp [2d x 3d], UcTp [d x d], b [3d] as for bmp_ggnn_step_fwd;
+ *      BTp [d x d] = B^T (K-major), K4-packed.  Saves m [N x d], rz [N x 2d], c [N x d] (all three may be NULL together:
+ *      forward-only evaluation) and writes hout [N x d].  first != 0: the r half of rz is not written, UcTp is not read.
+ * bwd: Wnat_p [d x 4d], A_p [3d x 2d], Uc_p [d x d] as for bmp_ggnn_step_bwd; B_p [d x d] = B as [out x in], K4-packed.
+ *      Writes dh [N x d], gda [N x 8d] = [G_0 .. G_3 | Q | da_r | da_z | da_c] with Q_r = row_w[r] * (the sum of dm over the
+ *      rows of r's molecule), and, for later calls, rh [N x d] = r * h.  first != 0: the da_r block is written as zeros, rh
+ *      is not written and may be NULL, Uc_p is not read.
+ * Weight gradients: the three calls of bmp_linear_wgrad described for bmp_ggnn_loop_step_*: X = h against the Q block gives
+ * dB^T.  The column sums of the first five blocks mean nothing here (the message has no bias).
+ * No allocation, no host sync; every row array 16-byte aligned. */
+int bmp_ggnn_edge_step_supported(int d);
+int bmp_ggnn_edge_step_tile_fwd(const float* h, int n_tiles, int d, int first, const int* csr_ptr, const int* csr_col,
+                                const float* csr_val, const float* row_w, const int* row_mol, const int* mol_row0,
+                                const int* mol_nrows, int n_mols, const float* WTp, const float* BTp, const float* ATp,
+                                const float* UcTp, const float* b, float* m, float* rz, float* c, float* hout,
+                                bmp_stream_t stream);
+int bmp_ggnn_edge_step_tile_bwd(const float* dhout, const float* h, const float* rz, const float* c, int n_tiles, int d, int first,
+                                const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* row_w,
+                                const int* row_mol, const int* mol_row0, const int* mol_nrows, int n_mols, const float* Wnat_p,
+                                const float* B_p, const float* A_p, const float* Uc_p, float* dh, float* gda, float* rh,
+                                bmp_stream_t stream);
+
 /* ---- Neural-fingerprint encoder -- models/models/nfp.py (csrc/bmp_nfp.hip) ----
  * ONE adjacency: every bond counts once whatever its type (csr_col >> 2 is the source row), plus a self loop of weight
  * self_w [N] on the rows that have one (1 on real atoms, 0 on pad and dead rows).  deg_class [N] in 0..7: k when the COLUMN
