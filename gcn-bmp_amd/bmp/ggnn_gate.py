@@ -11,7 +11,8 @@ Both keep models/ggnn.py's embedding, its message (edge type the fastest axis of
     gate (ggnn_dev_gate.py:112-116):    a = sigmoid(Wg_k x + bg_k), out = (1 - a) * h + a * m,  k = 0 if update_tying else step
 
 The fuse linears are shared by all steps even when the message weights are untied.  A step is ``Fn.gate_step``: one fused
-kernel per tile and direction at hidden_dim 64 / 128 on whole tiles (csrc/bmp_gate.hip), the composed operators otherwise.
+kernel per tile and direction at hidden_dim 64 / 128 (csrc/bmp_gate.hip) and at 32, the recorded width (csrc/bmp_gate_small.hip,
+for the kinds Fn.GATE_SMALL_DEFAULT holds True for), on whole tiles; the composed operators otherwise.
 
 Dropout (the fuse gate's on ``r * h`` and ``dropout_rate`` on every step's output, :157-158): identity under ``eval()``; in
 training the zero-padded positions of a molecule are ONE row of the packed layout and share one mask, where the reference
@@ -38,7 +39,7 @@ class _GatedGGNN(nn.Module):
 
     NUM_EDGE_TYPE = NUM_EDGE_TYPE
     KIND = None                 # Fn.GATE_KIND of the subclass
-    _fused = True               # private switch: False takes the composed operators at every width
+    _fused = True               # private switch: False takes the composed operators at every width (32, 64 and 128 included)
 
     def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
         super().__init__()

@@ -233,6 +233,17 @@ int bmp_ggnn_gate_step_tile_fwd(int kind, const float* h, int n_tiles, int d, co
 int bmp_ggnn_gate_step_tile_bwd(int kind, const float* dhout, const float* h, const float* m, const float* act, const float* keep,
                                 int n_tiles, int d, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
                                 const float* Wnat_p, const float* Unat_p, float* dh, float* gda, bmp_stream_t stream);
+/* The same step at d = 32 (bmp_ggnn_gate_step_small_supported: 32 only; csrc/bmp_gate_small.hip): the argument lists, layouts,
+ * outputs and checks of the two _tile_ entries, so the same two bmp_linear_wgrad calls serve both.  One workgroup of 256 threads
+ * per 128-row tile, wave w owns the 32-row block w in every phase; 48 KB of LDS, one workgroup barrier per direction; the
+ * message products of a bond type are skipped for a wave whose 32 rows hold no bond of that type. */
+int bmp_ggnn_gate_step_small_supported(int d);
+int bmp_ggnn_gate_step_small_fwd(int kind, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col,
+                                 const float* csr_val, const float* WTp, const float* bE, const float* AUp, const float* bU,
+                                 const float* keep, float* m, float* act, float* hout, bmp_stream_t stream);
+int bmp_ggnn_gate_step_small_bwd(int kind, const float* dhout, const float* h, const float* m, const float* act, const float* keep,
+                                 int n_tiles, int d, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
+                                 const float* Wnat_p, const float* Unat_p, float* dh, float* gda, bmp_stream_t stream);
 
 /* ---- GGNN step with a per-atom self loop in the message -- models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py
  * (csrc/bmp_loop.hip) ----
