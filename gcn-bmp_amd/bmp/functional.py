@@ -1264,6 +1264,70 @@ def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# What the self-loop and the edge-network step share, as their kernels do (csrc/bmp_wtile_gru.h): the GRU step on whole tiles
+# with a fifth message operand of weight W5 [d x d] (WsT / BT).  ``kind``: 'loop' / 'edge', the C entries' infix.
+# ---------------------------------------------------------------------------------------------------------
+def _seg_args(pb, row_mol):
+    """The edge entries' segment arguments; the self-loop entries take none (row_mol None)."""
+    return [] if row_mol is None else [ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), pb.n_mols]
+
+
+def _gru_tile_fwd(ctx, kind, h, WT, W5, AT, UcT, b, pb, first, bE=None, bs=None):
+    """Shape checks, K4 packing, buffers (none but hout for forward-only evaluation), launch; (bE, bs): the self loop's biases."""
+    L = _lib.lib()
+    require_rows(h, f"{kind} step: h")
+    _check_pb(pb, h)
+    N, d = h.shape
+    if tuple(WT.shape) != (4 * d, d) or tuple(W5.shape) != (d, d) or tuple(AT.shape) != (2 * d, 3 * d) or tuple(UcT.shape) != (d, d) \
+            or tuple(b.shape) != (3 * d,) or (kind == "loop" and (tuple(bE.shape) != (4, d) or tuple(bs.shape) != (d,))):
+        raise ValueError(f"{kind} step: weight shapes do not match h")
+    if not (whole_tiles_ok(pb) and getattr(L, f"bmp_ggnn_{kind}_step_supported")(d)):
+        raise ValueError(f"{kind} step: the fused kernels take d in {{64, 128}} on whole tiles; use {kind}_step()")
+    b = b.contiguous()
+    WTp, W5p, ATp, UcTp = pack_k4(WT), pack_k4(W5), pack_k4(AT), pack_k4(UcT)
+    if kind == "loop":
+        bE, bs = bE.contiguous(), bs.contiguous()
+        w = [ptr(WTp), ptr(bE), ptr(W5p), ptr(bs)]
+    else:
+        w = [ptr(WTp), ptr(W5p)]
+    row_mol = _row_mol(pb) if kind == "edge" else None
+    f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+    infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
+    m, rz, c, hout = (None, None, None, f(d)) if infer else (f(d), f(2 * d), f(d), f(d))
+    name = f"bmp_ggnn_{kind}_step_tile_fwd"
+    check(getattr(L, name)(ptr(h), pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                           *_seg_args(pb, row_mol), *w, ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c), ptr(hout),
+                           stream()), name)
+    if not infer:
+        ctx.save_for_backward(h, WT, W5, AT, UcT, m, rz, c, *([] if row_mol is None else [row_mol]))
+    ctx.pb, ctx.first = pb, int(first)
+    return hout
+
+
+def _gru_tile_bwd(ctx, kind, dhout):
+    """(dh, dWT, dW5, dAT, dUcT, cs): cs the column sums of gda [N x 8d] = [G_0 .. G_3 | dm or Q | da_r | da_z | da_c], i.e. the
+    bias gradients dbE | dbs | db where the message has the bias."""
+    L = _lib.lib()
+    h, WT, W5, AT, UcT, m, rz, c, *row_mol = ctx.saved_tensors
+    pb, first = ctx.pb, ctx.first
+    dhout = dhout.contiguous()
+    N, d = h.shape
+    Wnat_p, W5_p, A_p, Uc_p = pack_k4(WT.t()), pack_k4(W5.t()), pack_k4(AT.t()), pack_k4(UcT.t())
+    f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+    dh, gda = f(d), f(8 * d)
+    rh = None if first else f(d)
+    name = f"bmp_ggnn_{kind}_step_tile_bwd"
+    check(getattr(L, name)(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_tiles, d, first, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
+                           ptr(pb.csrT_val), *_seg_args(pb, row_mol[0] if row_mol else None), ptr(Wnat_p), ptr(W5_p), ptr(A_p), ptr(Uc_p), ptr(dh),
+                           ptr(gda), ptr(rh), stream()), name)
+    o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dW5 | dAT's h half; all column sums
+    o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
+    dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
+    dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
+    return dh, dWT, o1[:, 4 * d:5 * d], torch.cat((o1[:, 5 * d:], o2), dim=0), dUcT, cs
+
+
+# ---------------------------------------------------------------------------------------------------------
 # GGNN step with a per-atom self loop in the message (models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py;
 # csrc/bmp_loop.hip).
 # ---------------------------------------------------------------------------------------------------------
@@ -1282,49 +1346,15 @@ class LoopStepFn(Function):
 
     @staticmethod
     def forward(ctx, h, WT, bE, WsT, bs, AT, UcT, b, pb, first):
-        L = _lib.lib()
-        require_rows(h, "loop step: h")
-        _check_pb(pb, h)
-        N, d = h.shape
-        if tuple(WT.shape) != (4 * d, d) or tuple(bE.shape) != (4, d) or tuple(WsT.shape) != (d, d) or tuple(bs.shape) != (d,) \
-                or tuple(AT.shape) != (2 * d, 3 * d) or tuple(UcT.shape) != (d, d) or tuple(b.shape) != (3 * d,):
-            raise ValueError("loop step: weight shapes do not match h")
-        if not (whole_tiles_ok(pb) and loop_step_supported(d)):
-            raise ValueError("loop step: the fused kernels take d in {64, 128} on whole tiles; use loop_step()")
-        bE, bs, b = bE.contiguous(), bs.contiguous(), b.contiguous()
-        WTp, WsTp, ATp, UcTp = pack_k4(WT), pack_k4(WsT), pack_k4(AT), pack_k4(UcT)
-        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
-        infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
-        m, rz, c, hout = (None, None, None, f(d)) if infer else (f(d), f(2 * d), f(d), f(d))
-        check(L.bmp_ggnn_loop_step_tile_fwd(ptr(h), pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
-                                            ptr(WTp), ptr(bE), ptr(WsTp), ptr(bs), ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c),
-                                            ptr(hout), stream()), "bmp_ggnn_loop_step_tile_fwd")
-        if not infer:
-            ctx.save_for_backward(h, WT, WsT, AT, UcT, m, rz, c)
-        ctx.pb, ctx.first = pb, int(first)
+        hout = _gru_tile_fwd(ctx, "loop", h, WT, WsT, AT, UcT, b, pb, first, bE, bs)
         LOOP_PATHS["fused"] += 1
         return hout
 
     @staticmethod
     def backward(ctx, dhout):
-        L = _lib.lib()
-        h, WT, WsT, AT, UcT, m, rz, c = ctx.saved_tensors
-        pb, first = ctx.pb, ctx.first
-        dhout = dhout.contiguous()
-        N, d = h.shape
-        Wnat_p, Ws_p, A_p, Uc_p = pack_k4(WT.t()), pack_k4(WsT.t()), pack_k4(AT.t()), pack_k4(UcT.t())
-        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
-        dh, gda = f(d), f(8 * d)
-        rh = None if first else f(d)
-        check(L.bmp_ggnn_loop_step_tile_bwd(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_tiles, d, first, ptr(pb.csrT_ptr),
-                                            ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Ws_p), ptr(A_p), ptr(Uc_p), ptr(dh),
-                                            ptr(gda), ptr(rh), stream()), "bmp_ggnn_loop_step_tile_bwd")
-        o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dWsT | dAT's h half; all column sums
-        o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
-        dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
-        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
-        return (dh, dWT, cs[:4 * d].reshape(4, d), o1[:, 4 * d:5 * d], cs[4 * d:5 * d], torch.cat((o1[:, 5 * d:], o2), dim=0), dUcT,
-                cs[5 * d:], None, None)
+        dh, dWT, dWsT, dAT, dUcT, cs = _gru_tile_bwd(ctx, "loop", dhout)
+        d = dh.shape[1]
+        return dh, dWT, cs[:4 * d].reshape(4, d), dWsT, cs[4 * d:5 * d], dAT, dUcT, cs[5 * d:], None, None
 
 
 def loop_step(h, WT, bE, WsT, bs, AT, UcT, b, first, pb, fused=True, state=None, state_w=None):
@@ -1373,51 +1403,14 @@ class EdgeStepFn(Function):
 
     @staticmethod
     def forward(ctx, h, WT, BT, AT, UcT, b, pb, first):
-        L = _lib.lib()
-        require_rows(h, "edge step: h")
-        _check_pb(pb, h)
-        N, d = h.shape
-        if tuple(WT.shape) != (4 * d, d) or tuple(BT.shape) != (d, d) or tuple(AT.shape) != (2 * d, 3 * d) \
-                or tuple(UcT.shape) != (d, d) or tuple(b.shape) != (3 * d,):
-            raise ValueError("edge step: weight shapes do not match h")
-        if not (whole_tiles_ok(pb) and edge_step_supported(d)):
-            raise ValueError("edge step: the fused kernels take d in {64, 128} on whole tiles; use edge_step()")
-        b = b.contiguous()
-        WTp, BTp, ATp, UcTp = pack_k4(WT), pack_k4(BT), pack_k4(AT), pack_k4(UcT)
-        row_mol = _row_mol(pb)
-        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
-        infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
-        m, rz, c, hout = (None, None, None, f(d)) if infer else (f(d), f(2 * d), f(d), f(d))
-        check(L.bmp_ggnn_edge_step_tile_fwd(ptr(h), pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
-                                            ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), pb.n_mols, ptr(WTp),
-                                            ptr(BTp), ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c), ptr(hout), stream()),
-              "bmp_ggnn_edge_step_tile_fwd")
-        if not infer:
-            ctx.save_for_backward(h, WT, BT, AT, UcT, m, rz, c, row_mol)
-        ctx.pb, ctx.first = pb, int(first)
+        hout = _gru_tile_fwd(ctx, "edge", h, WT, BT, AT, UcT, b, pb, first)
         EDGE_PATHS["fused"] += 1
         return hout
 
     @staticmethod
     def backward(ctx, dhout):
-        L = _lib.lib()
-        h, WT, BT, AT, UcT, m, rz, c, row_mol = ctx.saved_tensors
-        pb, first = ctx.pb, ctx.first
-        dhout = dhout.contiguous()
-        N, d = h.shape
-        Wnat_p, B_p, A_p, Uc_p = pack_k4(WT.t()), pack_k4(BT.t()), pack_k4(AT.t()), pack_k4(UcT.t())
-        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
-        dh, gda = f(d), f(8 * d)
-        rh = None if first else f(d)
-        check(L.bmp_ggnn_edge_step_tile_bwd(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_tiles, d, first, ptr(pb.csrT_ptr),
-                                            ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0),
-                                            ptr(pb.mol_nrows), pb.n_mols, ptr(Wnat_p), ptr(B_p), ptr(A_p), ptr(Uc_p), ptr(dh), ptr(gda),
-                                            ptr(rh), stream()), "bmp_ggnn_edge_step_tile_bwd")
-        o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dBT | dAT's h half; cs: db in its last 3d
-        o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
-        dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
-        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
-        return dh, dWT, o1[:, 4 * d:5 * d], torch.cat((o1[:, 5 * d:], o2), dim=0), dUcT, cs[5 * d:], None, None
+        dh, dWT, dBT, dAT, dUcT, cs = _gru_tile_bwd(ctx, "edge", dhout)
+        return dh, dWT, dBT, dAT, dUcT, cs[5 * dh.shape[1]:], None, None
 
 
 def edge_step(h, WT, BT, AT, UcT, b, first, pb, fused=True, state=None, state_w=None):

@@ -261,6 +261,46 @@ def as_packed(atom_array, adj, device) -> PackedMolBatch:
     return pack_from_dense([a.astype(np.int32)], [j.astype(np.float32)], device=device)
 
 
+class _StepEncoder(nn.Module):
+    """What the encoders of bmp/ggnn_dev.py and bmp/ggnn_gate.py share: constructor checks, the embedding and message links, the
+    readout links and the readout.  A subclass registers its own links between ``__init__`` and ``_make_readout()``, in its
+    reference file's order (the snapshots map key by key)."""
+
+    NUM_EDGE_TYPE = NUM_EDGE_TYPE
+
+    def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
+        super().__init__()
+        if batch_normalization:     # (the files store the flag and never read it; refused like GGNN's)
+            raise NotImplementedError("batch_normalization=True is not supported")
+        if not 0.0 <= dropout_rate < 1.0:
+            raise ValueError("dropout_rate must lie in [0, 1)")
+        if hidden_dim % 8:
+            raise ValueError("hidden_dim must be a multiple of 8 for the MFMA kernels")
+        if out_dim % 4:
+            raise ValueError("out_dim must be a multiple of 4")
+        self.out_dim, self.hidden_dim, self.n_layers = out_dim, hidden_dim, n_layers
+        self.concat_hidden, self.dropout_rate, self.weight_tying = concat_hidden, dropout_rate, weight_tying
+        self.batch_normalization = batch_normalization
+        self.n_readout_layer = n_layers if concat_hidden else 1
+        self.n_message_layer = 1 if weight_tying else n_layers
+        self.embed = EmbedID(out_size=hidden_dim, in_size=n_atom_types)
+        self.message_layers = nn.ModuleList([Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
+
+    def _make_readout(self):
+        self.i_layers = nn.ModuleList([Linear(2 * self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
+        self.j_layers = nn.ModuleList([Linear(self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
+
+    def plannable(self) -> bool:
+        return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
+
+    def readout(self, h, h0, pb, step=0):
+        """i sees [h, h0], j sees h only -> j's h0 rows are zero in the kernel layout."""
+        i, j = self.i_layers[step if self.concat_hidden else 0], self.j_layers[step if self.concat_hidden else 0]
+        d = self.hidden_dim
+        WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
+        return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
+
+
 class GGNN(nn.Module):
     NUM_EDGE_TYPE = NUM_EDGE_TYPE
 

@@ -31,46 +31,11 @@ from torch import nn
 
 from . import functional as Fn
 from .coarse import SegPoolFn
-from .ggnn import EmbedID, GRU, Linear, MAX_ATOMIC_NUM, NUM_EDGE_TYPE, PackedAtoms, _is_float_atoms, as_packed, message_kernel_weights
+from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
 
 
-class _DevBase(nn.Module):
-    """What the two files share: constructor checks, links, readout and the step loop (``_step`` is the subclass's)."""
-
-    NUM_EDGE_TYPE = NUM_EDGE_TYPE
-
-    def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
-        super().__init__()
-        if batch_normalization:     # (the files store the flag and never read it; refused like bmp.ggnn.GGNN's)
-            raise NotImplementedError("batch_normalization=True is not supported")
-        if not 0.0 <= dropout_rate < 1.0:
-            raise ValueError("dropout_rate must lie in [0, 1)")
-        if hidden_dim % 8:
-            raise ValueError("hidden_dim must be a multiple of 8 for the MFMA kernels")
-        if out_dim % 4:
-            raise ValueError("out_dim must be a multiple of 4")
-        self.out_dim, self.hidden_dim, self.n_layers = out_dim, hidden_dim, n_layers
-        self.concat_hidden, self.dropout_rate, self.weight_tying = concat_hidden, dropout_rate, weight_tying
-        self.batch_normalization = batch_normalization
-        self.n_readout_layer = n_layers if concat_hidden else 1
-        self.n_message_layer = 1 if weight_tying else n_layers
-        self.embed = EmbedID(out_size=hidden_dim, in_size=n_atom_types)
-        self.message_layers = nn.ModuleList([Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
-
-    def _make_update_and_readout(self):
-        self.update_layer = GRU(2 * self.hidden_dim, self.hidden_dim)
-        self.i_layers = nn.ModuleList([Linear(2 * self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
-        self.j_layers = nn.ModuleList([Linear(self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
-
-    def plannable(self) -> bool:
-        return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
-
-    def readout(self, h, h0, pb, step=0):
-        """i sees [h, h0], j sees h only -> j's h0 rows are zero in the kernel layout."""
-        i, j = self.i_layers[step if self.concat_hidden else 0], self.j_layers[step if self.concat_hidden else 0]
-        d = self.hidden_dim
-        WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
-        return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
+class _DevBase(_StepEncoder):
+    """What the two files share beyond _StepEncoder: the step loop (``_step`` is the subclass's) and the GRU's weights."""
 
     def _steps(self, atom_array, adj):
         """embed + the propagation steps: (pb, h0, [h after every step, dropout applied])."""
@@ -122,7 +87,8 @@ class DevGGNN(_DevBase):
                  batch_normalization=False, weight_tying=True, output_atoms=True):
         super().__init__(out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying)
         self.output_atoms = output_atoms
-        self._make_update_and_readout()
+        self.update_layer = GRU(2 * hidden_dim, hidden_dim)
+        self._make_readout()
         self.atoms_list, self.g_vec_list = [], []
 
     def _step(self, h, step, ctx):
@@ -178,7 +144,8 @@ class SelfLoopGGNN(_DevBase):
                  batch_normalization=False, weight_tying=True):
         super().__init__(out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying)
         self.message_self_loop_layers = nn.ModuleList([Linear(hidden_dim, hidden_dim) for _ in range(self.n_message_layer)])
-        self._make_update_and_readout()
+        self.update_layer = GRU(2 * hidden_dim, hidden_dim)
+        self._make_readout()
         self.atoms = None
 
     def _step(self, h, step, ctx):

@@ -29,50 +29,17 @@ import torch
 from torch import nn
 
 from . import functional as Fn
-from .ggnn import EmbedID, GRU, Linear, MAX_ATOMIC_NUM, NUM_EDGE_TYPE, PackedAtoms, _is_float_atoms, as_packed, message_kernel_weights
+from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
 
 FUSE_DROPOUT = 0.05             # models/ggnn_dev_fuse.py:127
 
 
-class _GatedGGNN(nn.Module):
-    """What the two files share: constructor checks, embedding, message layers, readout and the step loop."""
+class _GatedGGNN(_StepEncoder):
+    """What the two files share beyond _StepEncoder (its readout is :133-141): the step loop."""
 
-    NUM_EDGE_TYPE = NUM_EDGE_TYPE
     KIND = None                 # Fn.GATE_KIND of the subclass
     _fused = True               # private switch: False takes the composed operators at every width (32, 64 and 128 included)
-
-    def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
-        super().__init__()
-        if batch_normalization:     # (the files store the flag and never read it; refused like bmp.ggnn.GGNN's)
-            raise NotImplementedError("batch_normalization=True is not supported")
-        if not 0.0 <= dropout_rate < 1.0:
-            raise ValueError("dropout_rate must lie in [0, 1)")
-        if hidden_dim % 8:
-            raise ValueError("hidden_dim must be a multiple of 8 for the MFMA kernels")
-        if out_dim % 4:
-            raise ValueError("out_dim must be a multiple of 4")
-        self.out_dim, self.hidden_dim, self.n_layers = out_dim, hidden_dim, n_layers
-        self.concat_hidden, self.dropout_rate, self.weight_tying = concat_hidden, dropout_rate, weight_tying
-        self.batch_normalization = batch_normalization
-        self.n_readout_layer = n_layers if concat_hidden else 1
-        self.n_message_layer = 1 if weight_tying else n_layers
-        self.embed = EmbedID(out_size=hidden_dim, in_size=n_atom_types)
-        self.message_layers = nn.ModuleList([Linear(hidden_dim, NUM_EDGE_TYPE * hidden_dim) for _ in range(self.n_message_layer)])
-        self.atoms = None
-
-    def _make_readout(self):
-        self.i_layers = nn.ModuleList([Linear(2 * self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
-        self.j_layers = nn.ModuleList([Linear(self.hidden_dim, self.out_dim) for _ in range(self.n_readout_layer)])
-
-    def plannable(self) -> bool:
-        return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
-
-    def readout(self, h, h0, pb, step=0):
-        """:133-141: i sees [h, h0], j sees h only -> j's h0 rows are zero in the kernel layout."""
-        i, j = self.i_layers[step if self.concat_hidden else 0], self.j_layers[step if self.concat_hidden else 0]
-        d = self.hidden_dim
-        WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
-        return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
+    atoms = None                # the last call's atom states (get_atom_array)
 
     def _update_weights(self, step):
         """(AU [2d x Nu], bU [Nu]) of the step, in Fn.gate_step's layout."""

@@ -18,18 +18,11 @@
 // h and m never leave the CU between the gather and the update.  The weight gradients are the caller's two calls of
 // bmp_linear_wgrad on gda: X = h over all of gda's columns, X = m over its last Nu.
 // Weights are K4-packed ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
+// The typed message phase reads like the GRU step body's (bmp_wtile_gru.h) and stays inline here: it has no fifth operand to
+// switch on, and as a function shared with that body it would be the per-phase split that spills there.
 #include "bmp_wtile.h"
 
 enum { GATE_FUSE = 0, GATE_SIMPLE = 1 };
-
-// rows [row0, row0 + 128) of the row-major g [.. x ldg], columns [coff, coff + D) := tile, 16 bytes per lane
-template <int D>
-__device__ __forceinline__ void gate_store_tile(const float* tile, float* __restrict__ g, int ldg, int coff, int row0, int tid) {
-    for (int i = tid; i < WT_R * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        *(f32x4*)(g + (size_t)(row0 + r) * ldg + coff + 4 * q4) = *(const f32x4*)(tile + r * (D + 4) + 4 * q4);
-    }
-}
 
 template <int D, int KIND>
 __device__ __forceinline__ void gate_step_fwd(const float* __restrict__ h, const int* __restrict__ ptr, const int* __restrict__ col,
@@ -64,12 +57,7 @@ __device__ __forceinline__ void gate_step_fwd(const float* __restrict__ h, const
             wt_block_mma<NB, false>(am, tb + aoff, WTp + (size_t)e * D * D + ((size_t)(wv.lane >> 5) * D + bcol) * 4, D, D);
             __syncthreads();
         }
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int c = wt_col(wv, NB, nb);
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) tb[wt_row(wv, reg) * LD + c] = am[nb][reg];
-        }
+        wt_acc_to_tile<D>(tb, am, wv);
     }
     __syncthreads();
     {   // + sum_e wdeg_e b_e, by the thread that took the row's weighted degrees
@@ -122,16 +110,11 @@ __device__ __forceinline__ void gate_step_fwd(const float* __restrict__ h, const
         for (int g = 0; g < NG; ++g) {
             float* t = (g & 1) ? tb : ta;                     // z -> A, r -> B, f -> A: one barrier between a store and the next fill
             if (g != 1) __syncthreads();
-#pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const int c = wt_col(wv, NB, nb);
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) t[wt_row(wv, reg) * LD + c] = au[g][nb][reg];
-            }
+            wt_acc_to_tile<D>(t, au[g], wv);
             if (g != 0) {
                 __syncthreads();
-                if (g == 1) gate_store_tile<D>(ta, act, NU, 0, row0, tid);
-                gate_store_tile<D>(t, act, NU, g * D, row0, tid);
+                if (g == 1) wt_store_tile<D>(ta, act, NU, 0, row0, tid);
+                wt_store_tile<D>(t, act, NU, g * D, row0, tid);
             }
         }
     } else {
@@ -148,8 +131,8 @@ __device__ __forceinline__ void gate_step_fwd(const float* __restrict__ h, const
             }
         }
         __syncthreads();
-        gate_store_tile<D>(ta, hout, D, 0, row0, tid);
-        if (act) gate_store_tile<D>(tb, act, NU, 0, row0, tid);
+        wt_store_tile<D>(ta, hout, D, 0, row0, tid);
+        if (act) wt_store_tile<D>(tb, act, NU, 0, row0, tid);
     }
 }
 
@@ -228,12 +211,7 @@ __device__ __forceinline__ void gate_step_bwd(const float* __restrict__ dhout, c
             __syncthreads();
         }
     }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) ta[wt_row(wv, reg) * LD + c] = ad[0][nb][reg];       // (behind the loop's last barrier)
-    }
+    wt_acc_to_tile<D>(ta, ad[0], wv);                         // (behind the loop's last barrier)
     __syncthreads();
     for (int i = tid; i < WT_R * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);

@@ -114,12 +114,7 @@ __global__ __launch_bounds__(512) void k_gin_tile_bwd(const float* __restrict__ 
     }
     __syncthreads();
     wt_wave_mma<D>(acc, tb, LD, W1np, D, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) ta[wt_row(wv, reg) * LD + c] = acc[nb][reg];
-    }
+    wt_acc_to_tile<D>(ta, acc, wv);
     __syncthreads();
     {
         const int row = tid >> 2, q = tid & 3;

@@ -3,6 +3,7 @@
 // [128][d + 4] tiles in LDS used in turn; wave w owns the 32-row block w >> 1 of the operand tile and the column half w & 1 of
 // the product.
 // Weights are K4-packed ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
+// The GRU step that the self-loop and edge-network kernels share is one body on this machinery, in bmp_wtile_gru.h.
 // (The half-tile-group kernels of bmp_fused*.hip keep their own loop and gather in bmp_tile.h: tile_mma, tile_gather.)
 #pragma once
 #include "bmp_tile.h"
@@ -25,6 +26,26 @@ __device__ __forceinline__ void wt_load_tile(float* tile, const float* __restric
     for (int i = tid; i < WT_R * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);
         *(f32x4*)(tile + r * (D + 4) + 4 * q4) = *(const f32x4*)(g + (size_t)(row0 + r) * D + 4 * q4);
+    }
+}
+
+// rows [row0, row0 + 128) of the row-major g [.. x ldg], columns [coff, coff + D) := tile, 16 bytes per lane
+template <int D>
+__device__ __forceinline__ void wt_store_tile(const float* tile, float* __restrict__ g, int ldg, int coff, int row0, int tid) {
+    for (int i = tid; i < WT_R * (D / 4); i += 512) {
+        const int r = i / (D / 4), q4 = i % (D / 4);
+        *(f32x4*)(g + (size_t)(row0 + r) * ldg + coff + 4 * q4) = *(const f32x4*)(tile + r * (D + 4) + 4 * q4);
+    }
+}
+
+// tile := a wave's accumulators, each lane its own (row, column) elements
+template <int D>
+__device__ __forceinline__ void wt_acc_to_tile(float* tile, const f32x16 (&acc)[D / 64], WtWave wv) {
+#pragma unroll
+    for (int nb = 0; nb < D / 64; ++nb) {
+        const int c = wt_col(wv, D / 64, nb);
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) tile[wt_row(wv, reg) * (D + 4) + c] = acc[nb][reg];
     }
 }
 

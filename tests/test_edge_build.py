@@ -151,3 +151,10 @@ def test_edge_kernels_have_no_scratch():
     scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
     assert len(names) == len(scratch) == 8, names             # forward and backward x first and later call x d = 64 and 128
     assert all(s == 0 for s in scratch), dict(zip(names, scratch))
+    # and no fewer waves per SIMD than the kernels were written for: (d = 128, d = 64) per kernel
+    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", r.stderr)]
+    floor = {"first_tile_fwd": (2, 5), "later_tile_fwd": (2, 5), "first_tile_bwd": (3, 5), "later_tile_bwd": (2, 3)}
+    assert len(occ) == 8, occ
+    for n, o in zip(names, occ):
+        *kind, d = re.search(r"k_edge_step_(\w+?)ILi(\d+)E", n).groups()
+        assert o >= floor["_".join(kind)][d == "64"], (n, o)
