@@ -84,6 +84,12 @@ SIGNATURES = {
     "bmp_ggnn_edge_step_supported": (_I, [_I]),
     "bmp_ggnn_edge_step_tile_fwd": (_I, [_P, _I, _I, _I] + [_P] * 7 + [_I] + [_P] * 10),
     "bmp_ggnn_edge_step_tile_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I] + [_P] * 7 + [_I] + [_P] * 8),
+    "bmp_jk_step_supported": (_I, [_I]),
+    "bmp_jk_step_tile_fwd": (_I, [_I, _P, _I, _I] + [_P] * 12),
+    "bmp_jk_step_tile_bwd": (_I, [_I, _P, _P, _I, _I] + [_P] * 9),
+    "bmp_jk_agg_ws_floats": (_Z, [_I, _I]),
+    "bmp_jk_agg_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _Z, _P, _P, _P]),
+    "bmp_jk_agg_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _Z, _P, _P]),
     "bmp_readout_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P]),
     "bmp_readout_bwd_ws_floats": (_Z, [_I, _I, _I, _I]),
     "bmp_readout_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _Z, _P, _P]),

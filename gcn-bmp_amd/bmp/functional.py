@@ -1526,3 +1526,150 @@ class PLayerAggFn(Function):
             acc = 0 if _first_write(ctx.state, "agg") else 1        # the encoder called once per side: the second call adds
         dhs = _agg_bwd(dy, hs, mode, ctx.W, ctx.b, ctx.aux, G["dW"] if mode == 1 else None, G["db"] if mode == 1 else None, acc)
         return (None, None, None, None, *dhs)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The jumping-knowledge GGNN encoders (models/ggnn_dev_jknet.py:99-142, models/ggnn_dev_jk_gru.py:74-120; csrc/bmp_jk.hip): a step
+# whose update is out = relu([h, m] . AU + bU) with no gate -- Nu = d columns (jknet: the whole update) or 2d (jk_gru: the layer
+# in front of its GRU) -- and the parameter-free 'mean' / 'attn' layer aggregators (ggnn_dev_jknet.py:215-226, 297-344).
+# ---------------------------------------------------------------------------------------------------------
+JK_PATHS = {"fused": 0, "composed": 0}           # forward calls per form
+# (kind, d): the fused step is the default where it beat the composed form by more than the two forms' spreads on the MI355X in at
+# least three of four runs (tools/jk_probe.py, profiles/jk_probe.json); an entry set to False goes through the
+# composed form.  Kind by the update's width: 'jknet' Nu = d, 'jk_gru' Nu = 2d.
+JK_STEP_DEFAULT = {("jknet", 64): True, ("jknet", 128): True, ("jk_gru", 64): True, ("jk_gru", 128): True}
+JK_AGG_MODE = {"mean": 0, "attn": 1}
+
+
+def jk_step_supported(d: int) -> bool:
+    return bool(_lib.lib().bmp_jk_step_supported(int(d)))
+
+
+class JKStepFn(Function):
+    """One propagation step -- the GGNN message (plus the self loop h . WsT + bs where WsT is given), then relu([h, m] . AU + bU) --
+    as ONE fused kernel per tile and direction.  WT [4d x d], bE [4 x d]: the message weights as MsgFn takes them; WsT [d x d]
+    K-major and bs [d], or None for both; AU [2d x Nu] K-major, rows [h-part; m-part], Nu = d or 2d; bU [Nu].  Returns [N x Nu].
+    d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes go through ``jk_step``."""
+
+    @staticmethod
+    def forward(ctx, h, WT, bE, WsT, bs, AU, bU, pb):
+        L = _lib.lib()
+        require_rows(h, "jk step: h")
+        _check_pb(pb, h)
+        N, d = h.shape
+        nu = AU.shape[1]
+        loop = WsT is not None
+        if nu not in (d, 2 * d) or tuple(WT.shape) != (4 * d, d) or tuple(bE.shape) != (4, d) or tuple(AU.shape) != (2 * d, nu) \
+                or tuple(bU.shape) != (nu,) or (bs is None) == loop or (loop and (tuple(WsT.shape) != (d, d) or tuple(bs.shape) != (d,))):
+            raise ValueError("jk step: weight shapes do not match h")
+        if not (whole_tiles_ok(pb) and jk_step_supported(d)):
+            raise ValueError("jk step: the fused kernels take d in {64, 128} on whole tiles; use jk_step()")
+        bE, bU = bE.contiguous(), bU.contiguous()
+        bs = bs.contiguous() if loop else None
+        WTp, AUp = pack_k4(WT), pack_k4(AU)
+        WsTp = pack_k4(WsT) if loop else None
+        f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
+        infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
+        m, out = (None if infer else f(d)), f(nu)
+        check(L.bmp_jk_step_tile_fwd(nu // d, ptr(h), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp),
+                                     ptr(bE), ptr(WsTp), ptr(bs), ptr(AUp), ptr(bU), ptr(m), ptr(out), stream()), "bmp_jk_step_tile_fwd")
+        if not infer:
+            ctx.save_for_backward(h, WT, AU, m, out, WsT if loop else torch.empty(0))
+        ctx.pb, ctx.loop = pb, loop
+        JK_PATHS["fused"] += 1
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        L = _lib.lib()
+        h, WT, AU, m, out, WsT = ctx.saved_tensors
+        pb, loop = ctx.pb, ctx.loop
+        dout = dout.contiguous()
+        N, d = h.shape
+        nu = AU.shape[1]
+        Wnat_p, Unat_p = pack_k4(WT.t()), pack_k4(AU.t())
+        Ws_p = pack_k4(WsT.t()) if loop else None
+        p0 = (5 if loop else 4) * d                                  # gda = [G_0 .. G_3 | dm (self loop) | dpre]
+        dh = torch.empty(N, d, dtype=torch.float32, device=h.device)
+        gda = torch.empty(N, p0 + nu, dtype=torch.float32, device=h.device)
+        check(L.bmp_jk_step_tile_bwd(nu // d, ptr(dout), ptr(out), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val),
+                                     ptr(Wnat_p), ptr(Ws_p), ptr(Unat_p), ptr(dh), ptr(gda), stream()), "bmp_jk_step_tile_bwd")
+        o1, cs = _linear_wgrad(h, gda)                               # dWT as [k][e d + c] | dWsT | dAU's h half; all column sums
+        o2, _ = _linear_wgrad(m, gda[:, p0:], bias=False)            # dAU's m half
+        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
+        return (dh, dWT, cs[:4 * d].reshape(4, d), o1[:, 4 * d:p0] if loop else None, cs[4 * d:p0] if loop else None,
+                torch.cat((o1[:, p0:], o2), dim=0), cs[p0:], None)
+
+
+def jk_step(h, WT, bE, WsT, bs, AU, bU, pb, fused=True):
+    """One step of the jknet (AU 2d x d) / jk_gru (AU 2d x 2d, in front of the GRU) encoders; the weight layouts are JKStepFn's.
+    The fused kernels where the tensors are on the GPU, the width is supported (64, 128, and JK_STEP_DEFAULT holds True for it)
+    and no molecule spans tiles; otherwise the existing operators, for any width that is a multiple of 8: the message operator
+    (with its self connection) and the row linear with relu on [h, m].  Both are differentiable through autograd."""
+    d = h.shape[1]
+    kind = "jknet" if AU.shape[1] == d else "jk_gru"
+    if fused and h.is_cuda and whole_tiles_ok(pb) and jk_step_supported(d) and JK_STEP_DEFAULT.get((kind, d), True):
+        return JKStepFn.apply(h, WT, bE, WsT, bs, AU, bU, pb)
+    JK_PATHS["composed"] += 1
+    m = MsgFn.apply(h, WT, bE, WsT, bs, pb, ACT["identity"])
+    return LinearRowsFn.apply(torch.cat((h, m), dim=1), AU, bU, ACT["relu"])
+
+
+def _jk_side_tiles(pb):
+    import ctypes
+    st = tuple(pb.side_tiles) if len(pb.side_tiles) > 1 else (0, pb.n_tiles)
+    if st[0] != 0 or st[-1] != pb.n_tiles or len(st) > 5:
+        raise ValueError(f"jk aggregator: the batch sides must be 1..4 contiguous tile ranges covering the batch, got {st}")
+    return (ctypes.c_int * len(st))(*st), len(st) - 1
+
+
+class JKAggFn(Function):
+    """The 'mean' / 'attn' aggregators of models/ggnn_dev_jknet.py:215-226, 297-344 over the step outputs ``hs`` ([N x d] each,
+    T <= AGG_MAX_T); ``mode`` from JK_AGG_MODE.  'attn': E_t = <H_t, H_T> + <H_t, H_1> over ALL positions of one batch side (rows
+    weighted by row_w, sides = pb.side_tiles), c = softmax_t(E), y = sum_t c_t H_t.  ``coef`` ([n_sides x T], the last call's
+    coefficients) is kept on the Function's context and returned through ``last_coef`` for inspection."""
+
+    last_coef = None
+
+    @staticmethod
+    def forward(ctx, mode, pb, *hs):
+        L = _lib.lib()
+        T = len(hs)
+        if mode not in (0, 1):
+            raise ValueError(f"jk aggregator mode must be 0 (mean) or 1 (attn), got {mode!r}")
+        if not 1 <= T <= AGG_MAX_T:
+            raise ValueError(f"jk aggregator: 1 <= n_layers <= {AGG_MAX_T}, got {T}")
+        N, d = require_rows(hs[0], "jk agg: h[0]").shape
+        _check_pb(pb, hs[0])
+        if d % 4:
+            raise ValueError("jk aggregator: the row width must be a multiple of 4")
+        for t in range(1, T):
+            if require_rows(hs[t], f"jk agg: h[{t}]", d).shape[0] != N:
+                raise ValueError("jk aggregator: the step tensors differ in their row count")
+        sides, ns = _jk_side_tiles(pb)
+        dev = hs[0].device
+        y = torch.empty(N, d, dtype=torch.float32, device=dev)
+        coef = torch.empty(ns, T, dtype=torch.float32, device=dev)
+        nws = L.bmp_jk_agg_ws_floats(pb.n_tiles, T)
+        ws = _ws(nws, dev)
+        check(L.bmp_jk_agg_fwd(_ptr_array(hs), T, pb.n_tiles, d, mode, ptr(pb.row_w), sides, ns, ptr(ws), nws, ptr(coef), ptr(y),
+                               stream()), "bmp_jk_agg_fwd")
+        ctx.save_for_backward(coef, *hs)
+        ctx.mode, ctx.pb = mode, pb
+        JKAggFn.last_coef = coef
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = _lib.lib()
+        coef, *hs = ctx.saved_tensors
+        pb, T = ctx.pb, len(hs)
+        N, d = hs[0].shape
+        dy = dy.contiguous()
+        sides, ns = _jk_side_tiles(pb)
+        dhs = [torch.empty_like(hs[0]) for _ in range(T)]
+        nws = L.bmp_jk_agg_ws_floats(pb.n_tiles, T)
+        ws = _ws(nws, dy.device)
+        check(L.bmp_jk_agg_bwd(ptr(dy), _ptr_array(hs), T, pb.n_tiles, d, ctx.mode, ptr(pb.row_w), sides, ns, ptr(coef), ptr(ws), nws,
+                               _ptr_array(dhs), stream()), "bmp_jk_agg_bwd")
+        return (None, None, *dhs)

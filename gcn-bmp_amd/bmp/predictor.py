@@ -150,9 +150,11 @@ def build_link_predictor(sim_method: str, fp_out_dim: int, class_num: int, net_h
 
 
 def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=True, attn: Optional[str] = "nie",
-                         head=8, class_num=1, encoder="ggnn", mlp_hidden=(32, 16), sim_method="mlp", dropout_ratio=0.5):
+                         head=8, class_num=1, encoder="ggnn", mlp_hidden=(32, 16), sim_method="mlp", dropout_ratio=0.5,
+                         layer_aggr="attn"):
     """set_up_predictor counterpart (train_binary.py:144-277) for the configs of BASELINE.json.  ``dropout_ratio``: the GIN
-    encoder's (the trainer builds it with 0.5); the other encoders do not read it."""
+    encoder's (the trainer builds it with 0.5); the other encoders do not read it.  ``layer_aggr``: the jknet encoder's layer
+    aggregator; the other encoders do not read it."""
     if encoder == "ggnn":
         enc = GGNN(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
     elif encoder == "ggnn-edge":                     # ggnn_hole.py:202, train_ggnn_hole_with_gwm.py:276: --message-function edge_network
@@ -176,6 +178,12 @@ def build_pair_predictor(hidden_dim=128, out_dim=128, n_layers=4, weight_tying=T
         from .ggnn_dev import DevGGNN, SelfLoopGGNN
         cls = DevGGNN if encoder == "ggnn-dev" else SelfLoopGGNN
         enc = cls(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
+    elif encoder in ("ggnn-jknet", "ggnn-jk-gru"):   # models/ggnn_dev_jknet.py, models/ggnn_dev_jk_gru.py: chosen by import
+        from .ggnn_jk import JKGruGGNN, JKNetGGNN
+        kw = dict(out_dim=out_dim, hidden_dim=hidden_dim, n_layers=n_layers, weight_tying=weight_tying)
+        # jknet's constructor fails without a layer aggregator (select_aggr asserts): 'attn', the file's own jumping-knowledge form
+        # jk_gru indexes its update layers by weight_tying: untied messages need untied update layers
+        enc = JKNetGGNN(layer_aggr=layer_aggr, **kw) if encoder == "ggnn-jknet" else JKGruGGNN(update_tying=weight_tying, **kw)
     else:
         raise ValueError('[ERROR] Invalid graph embedding encoder.')
     a = None

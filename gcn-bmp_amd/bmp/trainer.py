@@ -203,6 +203,9 @@ class PairBatches:
         on the padded atom count of its batch side, which the encoder layout and ``dedup`` give up (``fit`` asks before the first
         batch)."""
         enc = getattr(model, "graph_conv", model)
+        reason = getattr(enc, "layout_reason", None)     # bmp.ggnn_jk: layer_aggr='attn' couples the molecules of a batch side
+        if reason and self.layout in ("encoder", "static"):
+            raise NotImplementedError(f"PairBatches(layout={self.layout!r}, dedup={self.dedup}): " + reason)
         if getattr(enc, "message_function", None) != "edge_network":
             return
         if self.layout == "encoder":

@@ -245,6 +245,41 @@ int bmp_ggnn_gate_step_small_bwd(int kind, const float* dhout, const float* h, c
                                  int n_tiles, int d, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
                                  const float* Wnat_p, const float* Unat_p, float* dh, float* gda, bmp_stream_t stream);
 
+/* ---- The jumping-knowledge GGNN encoders -- models/ggnn_dev_jknet.py:99-142, 215-226, 297-344, models/ggnn_dev_jk_gru.py:74-120
+ * (csrc/bmp_jk.hip) ----
+ * The step: the message of bmp_ggnn_step_fwd, m = sum_e (agg_e . W_e + wdeg_e b_e) [+ h WsT + bs: the self loop of jk_gru], then
+ * out = relu([h, m] . AU + bU) with no gate, Nu = ng d columns wide: ng = 1 is the whole update of jknet, ng = 2 the 2d-wide layer
+ * in front of jk_gru's GRU (the GRU itself is bmp_gru_fwd / bmp_gru_state_fwd on the two halves of out).
+ * One kernel per direction, one workgroup per 128-row tile, d with bmp_jk_step_supported (64 or 128), exact-f32 MFMA; whole
+ * tiles whose molecules never straddle a tile (no tile table).  N = 128 n_tiles.
+ * fwd: WTp [4d x d] and bE [4 x d] as for bmp_ggnn_step_fwd; WsTp [d x d] K-major, K4-packed, and bs [d], both NULL for no self
+ *      loop; AUp [2d x Nu] K-major, rows [h-part; m-part], K4-packed; bU [Nu].  Saves m [N x d] (NULL: forward-only evaluation)
+ *      and writes out [N x Nu].
+ * bwd: reads the saved out for the relu mask.  Wnat_p [d x 4d] as for bmp_ggnn_step_bwd; Ws_p [d x d] = (WsT)^T, K4-packed, NULL
+ *      for no self loop; Unat_p [Nu x 2d] = AU^T, K4-packed.  Writes dh [N x d] and gda [N x ((4 + loop) d + Nu)] =
+ *      [G_0 .. G_3 | dm (self loop only) | dpre].
+ * Weight gradients: two calls of bmp_linear_wgrad -- X = h, dY = gda at full width gives dWT ([k][e d + c]), dWsT, the h half of dAU
+ * and all the column sums (dbE | dbs | dbU); X = m over gda's last Nu columns gives the m half of dAU.
+ * The aggregators of the T <= 8 step outputs h[t] [N x d] (host array of T device pointers), d a multiple of 4:
+ *   mode 0 'mean': y = (1 / T) sum_t h[t];  mode 1 'attn': E_t = sum_rows row_w (<h[t], h[T-1]> + <h[t], h[0]>) over the rows of ONE
+ *   batch side, c = softmax_t(E), y = sum_t c_t h[t].  side_tiles: n_sides + 1 host ints (n_sides <= 4), the tile boundaries of
+ *   the sides, read before the call returns.  fwd writes coef [n_sides x T] and y; bwd reads coef and writes every dh[t].
+ *   ws: bmp_jk_agg_ws_floats floats.  Sums in a fixed order, no atomics: bit-identical from run to run.
+ * No allocation, no host sync; every row array 16-byte aligned. */
+int bmp_jk_step_supported(int d);
+int bmp_jk_step_tile_fwd(int ng, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                         const float* WTp, const float* bE, const float* WsTp, const float* bs, const float* AUp, const float* bU,
+                         float* m, float* out, bmp_stream_t stream);
+int bmp_jk_step_tile_bwd(int ng, const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
+                         const float* csrT_val, const float* Wnat_p, const float* Ws_p, const float* Unat_p, float* dh, float* gda,
+                         bmp_stream_t stream);
+size_t bmp_jk_agg_ws_floats(int n_tiles, int T);
+int bmp_jk_agg_fwd(const float* const* h, int T, int n_tiles, int d, int mode, const float* row_w, const int* side_tiles,
+                   int n_sides, float* ws, size_t ws_floats, float* coef, float* y, bmp_stream_t stream);
+int bmp_jk_agg_bwd(const float* dy, const float* const* h, int T, int n_tiles, int d, int mode, const float* row_w,
+                   const int* side_tiles, int n_sides, const float* coef, float* ws, size_t ws_floats, float* const* dh,
+                   bmp_stream_t stream);
+
 /* ---- GGNN step with a per-atom self loop in the message -- models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py
  * (csrc/bmp_loop.hip) ----
  * The GRU step of bmp_ggnn_step_* with a fifth message operand: m = sum_e (agg_e . W_e + wdeg_e b_e) + h . W_s^T + b_s, then the
