@@ -78,6 +78,8 @@ SIGNATURES = {
     "bmp_ggnn_gate_step_small_supported": (_I, [_I]),
     "bmp_ggnn_gate_step_small_fwd": (_I, [_I, _P, _I, _I] + [_P] * 12),
     "bmp_ggnn_gate_step_small_bwd": (_I, [_I, _P, _P, _P, _P, _P, _I, _I] + [_P] * 8),
+    "bmp_ggnn_gate_step_small_table_fwd": (_I, [_I, _P, _I, _I] + [_P] * 13 + [_I, _I, _P]),
+    "bmp_ggnn_gate_step_small_table_bwd": (_I, [_I, _P, _P, _P, _P, _P, _I, _I] + [_P] * 9 + [_I, _I, _P]),
     "bmp_ggnn_loop_step_supported": (_I, [_I]),
     "bmp_ggnn_loop_step_tile_fwd": (_I, [_P, _I, _I, _I] + [_P] * 15),
     "bmp_ggnn_loop_step_tile_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I] + [_P] * 11),

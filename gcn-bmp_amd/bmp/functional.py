@@ -1165,6 +1165,11 @@ GATE_PATHS = {"fused": 0, "composed": 0}         # forward calls per form (a d =
 # MI355X in at least three of four runs (tools/gate_probe.py, profiles/gate_probe_d32.json); a kind set to False
 # here goes through the composed form.
 GATE_SMALL_DEFAULT = {"fuse": True, "gate": True}
+# d = 32 on a tile table (the encoder layout, with or without dedup, and the fixed-shape batch): the kinds whose table kernels
+# (the _table entries of csrc/bmp_gate_small.hip) beat the composed form by the same rule on the 1024-pair DDI-shaped batch in
+# both table layouts (tools/gate_table_probe.py, profiles/gate_table_probe.json); a kind set to False here stays
+# composed on table batches.  The d = 64 / 128 kernels take no table: a table batch at those widths is always composed.
+GATE_TABLE_DEFAULT = {"fuse": True, "gate": True}
 
 
 def gate_step_supported(d: int) -> bool:
@@ -1175,12 +1180,18 @@ def gate_step_small_supported(d: int) -> bool:
     return bool(_lib.lib().bmp_ggnn_gate_step_small_supported(int(d)))
 
 
+def gate_table_ok(pb, d: int) -> bool:
+    """The batch carries a tile table the d = 32 table kernels take (molecules never straddle the table's tiles)."""
+    return pb.mt_row0 is not None and not pb.oversized and gate_step_small_supported(d)
+
+
 class GateStepFn(Function):
     """One propagation step -- the GGNN message, then the fuse gate (kind 0) or the simple gate (kind 1) on x = [h, m] -- as ONE
     fused kernel per tile and direction.  WT [4d x d], bE [4 x d]: the message weights as MsgFn takes them; AU [2d x Nu] K-major,
     rows [h-part; m-part], columns [z | r | f] (Nu = 3d, fuse) or the gate's (Nu = d); bU [Nu]; keep [N x d] (0 or 1 / (1 - p), the
     dropout on r * h, fuse only) or None.  d in {32, 64, 128} (32: the wave-local kernels of csrc/bmp_gate_small.hip, the same
-    arguments), whole tiles (whole_tiles_ok); the other shapes go through ``gate_step``."""
+    arguments), whole tiles (whole_tiles_ok) or, at d = 32, a tile table (gate_table_ok: the grid is the table's pb.n_mtiles
+    entries); the other shapes go through ``gate_step``."""
 
     @staticmethod
     def forward(ctx, h, WT, bE, AU, bU, keep, pb, kind):
@@ -1193,8 +1204,10 @@ class GateStepFn(Function):
                 or tuple(bU.shape) != (nu,):
             raise ValueError("gate step: weight shapes do not match h")
         small = gate_step_small_supported(d)
-        if not (whole_tiles_ok(pb) and (small or gate_step_supported(d))):
-            raise ValueError("gate step: the fused kernels take d in {32, 64, 128} on whole tiles; use gate_step()")
+        table = gate_table_ok(pb, d)
+        if not (table or (whole_tiles_ok(pb) and (small or gate_step_supported(d)))):
+            raise ValueError("gate step: the fused kernels take d in {32, 64, 128} on whole tiles and d = 32 on a tile table; "
+                             "use gate_step()")
         if kind != 0:
             keep = None
         if keep is not None:
@@ -1206,10 +1219,16 @@ class GateStepFn(Function):
         f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
         infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
         m, act, hout = (None, None, f(d)) if infer else (f(d), f(nu), f(d))
-        fwd, name = (L.bmp_ggnn_gate_step_small_fwd, "bmp_ggnn_gate_step_small_fwd") if small else \
-            (L.bmp_ggnn_gate_step_tile_fwd, "bmp_ggnn_gate_step_tile_fwd")
-        check(fwd(kind, ptr(h), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp), ptr(bE), ptr(AUp), ptr(bU),
-                  ptr(keep), ptr(m), ptr(act), ptr(hout), stream()), name)
+        if table:
+            check(L.bmp_ggnn_gate_step_small_table_fwd(kind, ptr(h), pb.n_mtiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                                                       ptr(WTp), ptr(bE), ptr(AUp), ptr(bU), ptr(keep), ptr(m), ptr(act), ptr(hout),
+                                                       ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride, stream()),
+                  "bmp_ggnn_gate_step_small_table_fwd")
+        else:
+            fwd, name = (L.bmp_ggnn_gate_step_small_fwd, "bmp_ggnn_gate_step_small_fwd") if small else \
+                (L.bmp_ggnn_gate_step_tile_fwd, "bmp_ggnn_gate_step_tile_fwd")
+            check(fwd(kind, ptr(h), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp), ptr(bE), ptr(AUp),
+                      ptr(bU), ptr(keep), ptr(m), ptr(act), ptr(hout), stream()), name)
         if not infer:
             ctx.save_for_backward(h, WT, AU, m, act, keep if keep is not None else torch.empty(0))
         ctx.pb, ctx.kind, ctx.has_keep = pb, kind, keep is not None
@@ -1228,10 +1247,16 @@ class GateStepFn(Function):
         Wnat_p, Unat_p = pack_k4(WT.t()), pack_k4(AU.t())
         dh = torch.empty(N, d, dtype=torch.float32, device=h.device)
         gda = torch.empty(N, 4 * d + nu, dtype=torch.float32, device=h.device)
-        bwd, name = (L.bmp_ggnn_gate_step_small_bwd, "bmp_ggnn_gate_step_small_bwd") if gate_step_small_supported(d) else \
-            (L.bmp_ggnn_gate_step_tile_bwd, "bmp_ggnn_gate_step_tile_bwd")
-        check(bwd(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
-                  ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p), ptr(dh), ptr(gda), stream()), name)
+        if gate_table_ok(pb, d):
+            check(L.bmp_ggnn_gate_step_small_table_bwd(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_mtiles, d,
+                                                       ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p),
+                                                       ptr(dh), ptr(gda), ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride,
+                                                       stream()), "bmp_ggnn_gate_step_small_table_bwd")
+        else:
+            bwd, name = (L.bmp_ggnn_gate_step_small_bwd, "bmp_ggnn_gate_step_small_bwd") if gate_step_small_supported(d) else \
+                (L.bmp_ggnn_gate_step_tile_bwd, "bmp_ggnn_gate_step_tile_bwd")
+            check(bwd(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
+                      ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p), ptr(dh), ptr(gda), stream()), name)
         o1, cs = _linear_wgrad(h, gda)                               # [d x (4d + Nu)]: dWT as [k][e d + c] | dAU's h half; all column sums
         o2, _ = _linear_wgrad(m, gda[:, 4 * d:], bias=False)         # dAU's m half
         dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
@@ -1241,13 +1266,17 @@ class GateStepFn(Function):
 def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
     """One step of the fuse-gate (kind 0) / simple-gate (kind 1) GGNN; the weight layouts are GateStepFn's.  The fused kernels
     where the tensors are on the GPU, the width is supported (64, 128; 32 for the kinds GATE_SMALL_DEFAULT holds True for) and no
-    molecule spans tiles; otherwise the existing operators, for any width that is a multiple of 8: the message operator, the row
+    molecule spans tiles; on a batch with a tile table the d = 32 table kernels for the kinds GATE_TABLE_DEFAULT holds True for (a
+    table batch at 64 / 128 is composed); otherwise the existing operators, for any width that is a multiple of 8: the message operator, the row
     linear on [h, m] and torch's elementwise operators.  Both are differentiable through autograd."""
     d = h.shape[1]
     if kind != 0:
         keep = None
+    name = "gate" if kind else "fuse"
     if fused and h.is_cuda and whole_tiles_ok(pb) and (gate_step_supported(d) or (
-            GATE_SMALL_DEFAULT["gate" if kind else "fuse"] and gate_step_small_supported(d))):
+            GATE_SMALL_DEFAULT[name] and gate_step_small_supported(d))):
+        return GateStepFn.apply(h, WT, bE, AU, bU, keep, pb, kind)
+    if fused and h.is_cuda and GATE_TABLE_DEFAULT[name] and gate_table_ok(pb, d):
         return GateStepFn.apply(h, WT, bE, AU, bU, keep, pb, kind)
     GATE_PATHS["composed"] += 1
     m = MsgFn.apply(h, WT, bE, None, None, pb, ACT["identity"])

@@ -300,6 +300,10 @@ class _StepEncoder(nn.Module):
         WT = torch.cat((i.W.t(), torch.cat((j.W.t(), torch.zeros(d, self.out_dim, device=j.W.device, dtype=j.W.dtype)), dim=0)), dim=1)
         return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
 
+    def readout_rows(self, h, h0, pb):
+        """The readout of row tensors that live on ``pb``'s rows (the partner of a subclass's ``encode_rows``)."""
+        return self.readout(h, h0, pb, 0)
+
 
 class GGNN(nn.Module):
     NUM_EDGE_TYPE = NUM_EDGE_TYPE

@@ -12,7 +12,9 @@ Both keep models/ggnn.py's embedding, its message (edge type the fastest axis of
 
 The fuse linears are shared by all steps even when the message weights are untied.  A step is ``Fn.gate_step``: one fused
 kernel per tile and direction at hidden_dim 64 / 128 (csrc/bmp_gate.hip) and at 32, the recorded width (csrc/bmp_gate_small.hip,
-for the kinds Fn.GATE_SMALL_DEFAULT holds True for), on whole tiles; the composed operators otherwise.
+for the kinds Fn.GATE_SMALL_DEFAULT holds True for), on whole tiles; at 32 also on a tile table (the encoder layout, dedup,
+the static batch; Fn.GATE_TABLE_DEFAULT); the composed operators otherwise.  ``encode_rows`` / ``readout_rows`` serve the encoder
+layout: ``GateGGNN`` trains there, ``FuseGGNN`` takes it under ``eval()`` (its training dropout needs per-instance rows).
 
 Dropout (the fuse gate's on ``r * h`` and ``dropout_rate`` on every step's output, :157-158): identity under ``eval()``; in
 training the zero-padded positions of a molecule are ONE row of the packed layout and share one mask, where the reference
@@ -33,6 +35,16 @@ from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_fl
 
 FUSE_DROPOUT = 0.05             # models/ggnn_dev_fuse.py:127
 
+# encode_rows runs an encoder on the encoder layout's rows, where dedup gives all instances of a molecule ONE row set and every
+# tile one shared pad row: an active dropout would give those instances one mask, which is not the per-instance process.
+CONCAT_LAYOUT_REASON = ("concat_hidden=True reads out after every step on the per-instance rows; it takes the per-instance "
+                        "batch form")
+FUSE_TRAIN_LAYOUT_REASON = ("the fuse gate's dropout on r * h is active in training, and the encoder layout (dedup above all) "
+                            "would give all instances of a molecule one mask; train per-instance or on the static batch, or call "
+                            "eval()")
+DROPOUT_LAYOUT_REASON = ("dropout_rate > 0 is active in training, and the encoder layout (dedup above all) would give all "
+                         "instances of a molecule one mask; train per-instance or on the static batch, or call eval()")
+
 
 class _GatedGGNN(_StepEncoder):
     """What the two files share beyond _StepEncoder (its readout is :133-141): the step loop."""
@@ -52,6 +64,16 @@ class _GatedGGNN(_StepEncoder):
             raise NotImplementedError("float atom features (embedding bypass, models/ggnn_dev_fuse.py:149-150, "
                                       "models/ggnn_dev_gate.py:136-137) are not supported")
         pb = as_packed(atom_array, adj, self.embed.W.device)
+        g_list = [] if self.concat_hidden else None
+        h, h0 = self._steps(pb, g_list)
+        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+        if self.concat_hidden:
+            return torch.cat(g_list, dim=1)
+        return self.readout(h, h0, pb, 0)
+
+    def _steps(self, pb, g_list=None):
+        """The embedding and the propagation steps on the rows of ``pb``: (h, h0).  ``g_list`` collects the per-step readouts of
+        concat_hidden."""
         pb.check_atom_ids(self.embed.W.shape[0])
         h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
         h0 = h
@@ -60,7 +82,7 @@ class _GatedGGNN(_StepEncoder):
         masks = getattr(self, "_dropout_masks", None) if (self.training and fuse) else None
         if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
             raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
-        msgw, updw, g_list = {}, {}, []
+        msgw, updw = {}, {}
         for step in range(self.n_layers):
             li = 0 if self.weight_tying else step
             if li not in msgw:
@@ -77,12 +99,32 @@ class _GatedGGNN(_StepEncoder):
             h = Fn.gate_step(h, *msgw[li], *updw[ui], self.KIND, keep, pb, self._fused)
             if self.dropout_rate != 0.0 and self.training:              # :157-158, chainer: mask / (1 - ratio)
                 h = torch.nn.functional.dropout(h, p=self.dropout_rate, training=True)
-            if self.concat_hidden:
+            if g_list is not None:
                 g_list.append(self.readout(h, h0, pb, step))
-        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+        return h, h0
+
+    @property
+    def encoder_layout_reason(self):
+        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
+        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
+
+    def rows_reason(self):
+        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
         if self.concat_hidden:
-            return torch.cat(g_list, dim=1)
-        return self.readout(h, h0, pb, 0)
+            return CONCAT_LAYOUT_REASON
+        if self.training and self.KIND == Fn.GATE_KIND["fuse"]:
+            return FUSE_TRAIN_LAYOUT_REASON
+        if self.training and self.dropout_rate != 0.0:
+            return DROPOUT_LAYOUT_REASON
+        return None
+
+    def encode_rows(self, pb):
+        """The embedding and the steps WITHOUT the readout: (h, h0) on the rows of ``pb`` -- the entry the pair predictor uses
+        for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the per-instance rows (``readout_rows``)."""
+        reason = self.rows_reason()
+        if reason:
+            raise NotImplementedError("encode_rows: " + reason)
+        return self._steps(pb)
 
     def _update_index(self, step):
         return 0

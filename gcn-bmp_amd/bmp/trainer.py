@@ -206,6 +206,9 @@ class PairBatches:
         reason = getattr(enc, "layout_reason", None)     # bmp.ggnn_jk: layer_aggr='attn' couples the molecules of a batch side
         if reason and self.layout in ("encoder", "static"):
             raise NotImplementedError(f"PairBatches(layout={self.layout!r}, dedup={self.dedup}): " + reason)
+        reason = getattr(enc, "encoder_layout_reason", None)     # bmp.ggnn_gate: concat_hidden has no encode_rows
+        if reason and self.layout == "encoder":
+            raise NotImplementedError(f"PairBatches(layout='encoder', dedup={self.dedup}): " + reason)
         if getattr(enc, "message_function", None) != "edge_network":
             return
         if self.layout == "encoder":

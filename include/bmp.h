@@ -244,6 +244,22 @@ int bmp_ggnn_gate_step_small_fwd(int kind, const float* h, int n_tiles, int d, c
 int bmp_ggnn_gate_step_small_bwd(int kind, const float* dhout, const float* h, const float* m, const float* act, const float* keep,
                                  int n_tiles, int d, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
                                  const float* Wnat_p, const float* Unat_p, float* dh, float* gda, bmp_stream_t stream);
+/* The d = 32 step over a TILE TABLE (the encoder layout and the fixed-shape batch of bmp_ggnn_step_fwd): table entry t is the rows
+ * [mt_row0[t], mt_row0[t] + 32 mt_nblk[t]), mt_nblk in 1..4 live 32-row blocks; molecules never straddle entries and may straddle
+ * the blocks of one.  n_tiles counts the table's entries (the grid) and mt_rows is the row count N of the row arrays.  The waves of
+ * an entry's dead blocks gather, multiply and store nothing.  tile_stride: 0 for dense rows (entry t + 1 follows entry t), or the
+ * fixed row stride of the entries, a multiple of 32 that is >= 128; the rows [mt_row0[t] + 32 mt_nblk[t], mt_row0[t] + tile_stride)
+ * are then written as zeros in hout, m and act (fwd) and in dh and gda (bwd), so that the two bmp_linear_wgrad calls, which walk
+ * all N rows of h, m and gda, never read what an earlier batch left there.  Everything else as the two _small_ entries (the whole
+ * tiles of the d = 64 / 128 kernels above take no table).  No allocation, no host sync. */
+int bmp_ggnn_gate_step_small_table_fwd(int kind, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col,
+                                       const float* csr_val, const float* WTp, const float* bE, const float* AUp, const float* bU,
+                                       const float* keep, float* m, float* act, float* hout, const int* mt_row0, const int* mt_nblk,
+                                       int mt_rows, int tile_stride, bmp_stream_t stream);
+int bmp_ggnn_gate_step_small_table_bwd(int kind, const float* dhout, const float* h, const float* m, const float* act,
+                                       const float* keep, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
+                                       const float* csrT_val, const float* Wnat_p, const float* Unat_p, float* dh, float* gda,
+                                       const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, bmp_stream_t stream);
 
 /* ---- The jumping-knowledge GGNN encoders -- models/ggnn_dev_jknet.py:99-142, 215-226, 297-344, models/ggnn_dev_jk_gru.py:74-120
  * (csrc/bmp_jk.hip) ----
