@@ -83,6 +83,9 @@ SIGNATURES = {
     "bmp_ggnn_loop_step_supported": (_I, [_I]),
     "bmp_ggnn_loop_step_tile_fwd": (_I, [_P, _I, _I, _I] + [_P] * 15),
     "bmp_ggnn_loop_step_tile_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I] + [_P] * 11),
+    "bmp_ggnn_loop_step_table_supported": (_I, [_I]),
+    "bmp_ggnn_loop_step_table_fwd": (_I, [_P, _I, _I, _I] + [_P] * 16 + [_I, _I, _P]),
+    "bmp_ggnn_loop_step_table_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I] + [_P] * 12 + [_I, _I, _P]),
     "bmp_ggnn_edge_step_supported": (_I, [_I]),
     "bmp_ggnn_edge_step_tile_fwd": (_I, [_P, _I, _I, _I] + [_P] * 7 + [_I] + [_P] * 10),
     "bmp_ggnn_edge_step_tile_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I] + [_P] * 7 + [_I] + [_P] * 8),

@@ -1301,8 +1301,14 @@ def _seg_args(pb, row_mol):
     return [] if row_mol is None else [ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), pb.n_mols]
 
 
+def _table_args(pb, table):
+    """The tile-table arguments of the self loop's _table_ entries; the whole-tile entries take none."""
+    return [ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride] if table else []
+
+
 def _gru_tile_fwd(ctx, kind, h, WT, W5, AT, UcT, b, pb, first, bE=None, bs=None):
-    """Shape checks, K4 packing, buffers (none but hout for forward-only evaluation), launch; (bE, bs): the self loop's biases."""
+    """Shape checks, K4 packing, buffers (none but hout for forward-only evaluation), launch; (bE, bs): the self loop's biases.
+    The self loop takes whole tiles or a tile table (loop_table_ok: the grid is the table's pb.n_mtiles entries)."""
     L = _lib.lib()
     require_rows(h, f"{kind} step: h")
     _check_pb(pb, h)
@@ -1310,8 +1316,10 @@ def _gru_tile_fwd(ctx, kind, h, WT, W5, AT, UcT, b, pb, first, bE=None, bs=None)
     if tuple(WT.shape) != (4 * d, d) or tuple(W5.shape) != (d, d) or tuple(AT.shape) != (2 * d, 3 * d) or tuple(UcT.shape) != (d, d) \
             or tuple(b.shape) != (3 * d,) or (kind == "loop" and (tuple(bE.shape) != (4, d) or tuple(bs.shape) != (d,))):
         raise ValueError(f"{kind} step: weight shapes do not match h")
-    if not (whole_tiles_ok(pb) and getattr(L, f"bmp_ggnn_{kind}_step_supported")(d)):
-        raise ValueError(f"{kind} step: the fused kernels take d in {{64, 128}} on whole tiles; use {kind}_step()")
+    table = kind == "loop" and loop_table_ok(pb, d)
+    if not (table or (whole_tiles_ok(pb) and getattr(L, f"bmp_ggnn_{kind}_step_supported")(d))):
+        raise ValueError(f"{kind} step: the fused kernels take d in {{64, 128}} on whole tiles (the self loop: or on a tile table); "
+                         f"use {kind}_step()")
     b = b.contiguous()
     WTp, W5p, ATp, UcTp = pack_k4(WT), pack_k4(W5), pack_k4(AT), pack_k4(UcT)
     if kind == "loop":
@@ -1323,13 +1331,13 @@ def _gru_tile_fwd(ctx, kind, h, WT, W5, AT, UcT, b, pb, first, bE=None, bs=None)
     f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
     infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
     m, rz, c, hout = (None, None, None, f(d)) if infer else (f(d), f(2 * d), f(d), f(d))
-    name = f"bmp_ggnn_{kind}_step_tile_fwd"
-    check(getattr(L, name)(ptr(h), pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
-                           *_seg_args(pb, row_mol), *w, ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c), ptr(hout),
-                           stream()), name)
+    name = f"bmp_ggnn_{kind}_step_{'table' if table else 'tile'}_fwd"
+    check(getattr(L, name)(ptr(h), pb.n_mtiles if table else pb.n_tiles, d, int(first), ptr(pb.csr_ptr), ptr(pb.csr_col),
+                           ptr(pb.csr_val), *_seg_args(pb, row_mol), *w, ptr(ATp), ptr(UcTp), ptr(b), ptr(m), ptr(rz), ptr(c),
+                           ptr(hout), *_table_args(pb, table), stream()), name)
     if not infer:
         ctx.save_for_backward(h, WT, W5, AT, UcT, m, rz, c, *([] if row_mol is None else [row_mol]))
-    ctx.pb, ctx.first = pb, int(first)
+    ctx.pb, ctx.first, ctx.table = pb, int(first), table
     return hout
 
 
@@ -1338,17 +1346,17 @@ def _gru_tile_bwd(ctx, kind, dhout):
     bias gradients dbE | dbs | db where the message has the bias."""
     L = _lib.lib()
     h, WT, W5, AT, UcT, m, rz, c, *row_mol = ctx.saved_tensors
-    pb, first = ctx.pb, ctx.first
+    pb, first, table = ctx.pb, ctx.first, ctx.table
     dhout = dhout.contiguous()
     N, d = h.shape
     Wnat_p, W5_p, A_p, Uc_p = pack_k4(WT.t()), pack_k4(W5.t()), pack_k4(AT.t()), pack_k4(UcT.t())
     f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
     dh, gda = f(d), f(8 * d)
     rh = None if first else f(d)
-    name = f"bmp_ggnn_{kind}_step_tile_bwd"
-    check(getattr(L, name)(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_tiles, d, first, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
-                           ptr(pb.csrT_val), *_seg_args(pb, row_mol[0] if row_mol else None), ptr(Wnat_p), ptr(W5_p), ptr(A_p), ptr(Uc_p), ptr(dh),
-                           ptr(gda), ptr(rh), stream()), name)
+    name = f"bmp_ggnn_{kind}_step_{'table' if table else 'tile'}_bwd"
+    check(getattr(L, name)(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_mtiles if table else pb.n_tiles, d, first, ptr(pb.csrT_ptr),
+                           ptr(pb.csrT_col), ptr(pb.csrT_val), *_seg_args(pb, row_mol[0] if row_mol else None), ptr(Wnat_p), ptr(W5_p),
+                           ptr(A_p), ptr(Uc_p), ptr(dh), ptr(gda), ptr(rh), *_table_args(pb, table), stream()), name)
     o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dW5 | dAT's h half; all column sums
     o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
     dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
@@ -1360,18 +1368,30 @@ def _gru_tile_bwd(ctx, kind, dhout):
 # GGNN step with a per-atom self loop in the message (models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py;
 # csrc/bmp_loop.hip).
 # ---------------------------------------------------------------------------------------------------------
-LOOP_PATHS = {"fused": 0, "composed": 0}         # forward calls per form
+LOOP_PATHS = {"fused": 0, "composed": 0}         # forward calls per form (a table kernel call counts as fused)
+# On a tile table (the encoder layout, with or without dedup, and the fixed-shape batch): the widths whose table kernels (csrc/
+# bmp_loop_table.hip) beat the composed form, step forward + backward, by more than the two forms' p90 - median spreads together
+# in at least three of four runs on the 1024-pair DDI-shaped batch in BOTH table layouts (tools/loop_table_probe.py, profiles/
+# loop_table_probe.json); a width set to False here stays composed on table batches, its kernels reachable by
+# setting the entry.  Measured: both widths pass (d = 128 in 4 of 4 runs everywhere, d = 64 in 4 of 4 without and 3 of 4 with dedup).
+LOOP_TABLE_DEFAULT = {64: True, 128: True}
 
 
 def loop_step_supported(d: int) -> bool:
     return bool(_lib.lib().bmp_ggnn_loop_step_supported(int(d)))
 
 
+def loop_table_ok(pb, d: int) -> bool:
+    """The batch carries a tile table the self loop's table kernels take (molecules never straddle the table's tiles)."""
+    return pb.mt_row0 is not None and not pb.oversized and bool(_lib.lib().bmp_ggnn_loop_step_table_supported(int(d)))
+
+
 class LoopStepFn(Function):
     """One propagation step -- the GGNN message plus the self loop h . WsT + bs, then the GRU on [h, m] -- as ONE fused kernel per
     tile and direction.  WT [4d x d], bE [4 x d], AT [2d x 3d], UcT [d x d], b [3d]: as GGNNStepFn takes them (GRU.kernel_weights);
-    WsT [d x d] K-major (the transposed self-loop weight), bs [d].  d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes
-    go through ``loop_step``."""
+    WsT [d x d] K-major (the transposed self-loop weight), bs [d].  d in {64, 128}, whole tiles (whole_tiles_ok) or a tile table
+    (loop_table_ok); the other shapes go through ``loop_step``.  The weight gradients are three weight-gradient GEMMs on the
+    kernel's gda either way."""
 
     @staticmethod
     def forward(ctx, h, WT, bE, WsT, bs, AT, UcT, b, pb, first):
@@ -1388,12 +1408,15 @@ class LoopStepFn(Function):
 
 def loop_step(h, WT, bE, WsT, bs, AT, UcT, b, first, pb, fused=True, state=None, state_w=None):
     """One step of the self-loop GGNN; the weight layouts are LoopStepFn's.  The fused kernels where the tensors are on the GPU, the
-    width is supported and no molecule spans tiles; otherwise the existing operators, for any width that is a multiple of 8: the
+    width is supported and no molecule spans tiles; on a batch with a tile table the table kernels for the widths
+    LOOP_TABLE_DEFAULT holds True for; otherwise the existing operators, for any width that is a multiple of 8: the
     message operator with its self connection (WsT, bs) and no activation, then the GRU operator.  ``state`` (with ``state_w`` =
     GRU.kernel_weights_state(); training dropout, later calls): the GRU's own un-dropped state, apart from the dropped ``h`` -- the
     separate-state GRU operator, composed at every width (AT, UcT and b are then not read).  Differentiable through autograd."""
     d = h.shape[1]
     if state is None and fused and h.is_cuda and whole_tiles_ok(pb) and loop_step_supported(d):
+        return LoopStepFn.apply(h, WT, bE, WsT, bs, AT, UcT, b, pb, first)
+    if state is None and fused and h.is_cuda and LOOP_TABLE_DEFAULT.get(d, False) and loop_table_ok(pb, d):
         return LoopStepFn.apply(h, WT, bE, WsT, bs, AT, UcT, b, pb, first)
     LOOP_PATHS["composed"] += 1
     m = MsgFn.apply(h, WT, bE, WsT, bs, pb, ACT["identity"])

@@ -14,7 +14,12 @@ reset: no r gate, no U terms) and readout ``sum over ALL positions of sigmoid(i(
                   m = m + h W_s[l]^T + b_s[l], l = 0 if weight_tying else step (:96-97).  Padded positions have no bonds and one
                   h, so m = W_s h + b_s there too and the one virtual pad row per molecule stays exact.  A step is
                   ``Fn.loop_step``: one fused kernel per tile and direction at hidden_dim 64 / 128 on whole tiles
-                  (csrc/bmp_loop.hip), the composed operators otherwise.
+                  (csrc/bmp_loop.hip) and, for the widths Fn.LOOP_TABLE_DEFAULT holds True for, on a tile table -- the encoder
+                  layout, dedup, the static batch (csrc/bmp_loop_table.hip); the composed operators otherwise.
+
+``encode_rows`` / ``readout_rows`` serve the encoder layout (bmp/enclayout.py) for both classes, without ``concat_hidden`` and
+without an active dropout.  ``DevGGNN`` keeps only the last step's atom states then: ``get_atom_array()`` / ``get_atom_array(-1)``
+return them, any other step and ``get_g_list()`` raise.
 
 ``dropout_rate`` (after every step): identity under ``eval()``; in training the step OUTPUT is dropped while the stateful GRU keeps
 its own un-dropped state (the separate-state GRU operator), and the zero-padded positions of a molecule are ONE row of the packed
@@ -32,6 +37,10 @@ from torch import nn
 from . import functional as Fn
 from .coarse import SegPoolFn
 from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
+from .ggnn_gate import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON
+
+ROWS_ONLY_REASON = ("the last call ran in the encoder layout, where only the last step's atom states exist on the instance rows; "
+                    "per-step outputs need the per-instance batch form")
 
 
 class _DevBase(_StepEncoder):
@@ -62,6 +71,29 @@ class _DevBase(_StepEncoder):
             hs.append(h)
         return pb, h0, hs
 
+    @property
+    def encoder_layout_reason(self):
+        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
+        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
+
+    def rows_reason(self):
+        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
+        if self.concat_hidden:
+            return CONCAT_LAYOUT_REASON
+        if self.training and self.dropout_rate != 0.0:
+            return DROPOUT_LAYOUT_REASON
+        return None
+
+    def encode_rows(self, pb):
+        """The embedding and the steps WITHOUT the readout: (h after the last step, h0) on the rows of ``pb`` -- the entry the
+        pair predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the per-instance rows
+        (``readout_rows``)."""
+        reason = self.rows_reason()
+        if reason:
+            raise NotImplementedError("encode_rows: " + reason)
+        _, h0, hs = self._steps(pb, None)
+        return hs[-1], h0
+
     def _gru_weights(self, step, ctx):
         if step == 0:
             return self.update_layer.kernel_weights(first=True)
@@ -90,6 +122,7 @@ class DevGGNN(_DevBase):
         self.update_layer = GRU(2 * hidden_dim, hidden_dim)
         self._make_readout()
         self.atoms_list, self.g_vec_list = [], []
+        self._rows_only = False     # the last call was encode_rows: only the last step's atoms exist
 
     def _step(self, h, step, ctx):
         """bmp.ggnn.GGNN.forward's step, without the planned path."""
@@ -110,6 +143,7 @@ class DevGGNN(_DevBase):
         ignored).  Returns (n_mols, hidden_dim): the sum of the last step's atom states over ALL A positions (:165-168) --
         with concat_hidden (n_mols, n_layers * out_dim), the concatenated readouts."""
         self.atoms_list, self.g_vec_list = [], []               # :137-138
+        self._rows_only = False
         pb, h0, hs = self._steps(atom_array, adj)
         side = 0 if pb.dense_map is not None else None
         self.atoms_list = [PackedAtoms(h, pb, side) for h in hs]
@@ -124,13 +158,37 @@ class DevGGNN(_DevBase):
         """Width of what the call returns per molecule (the pair predictor sizes its link predictor by it)."""
         return self.n_layers * self.out_dim if self.concat_hidden else self.hidden_dim
 
+    def encode_rows(self, pb):
+        """_DevBase.encode_rows; what the last call kept of its steps is dropped (``set_rows_atoms`` hands over the new atoms)."""
+        self.atoms_list, self.g_vec_list = [], []
+        self._rows_only = True
+        return super().encode_rows(pb)
+
+    def readout_rows(self, h, h0, pb):
+        """What the call returns without concat_hidden, of row tensors that live on ``pb``'s rows: the sum of the last step's
+        atom states over all A positions (the pad row counts with its multiplicity pb.row_w), not the gated readout."""
+        ones = torch.ones(h.shape[0], 1, dtype=h.dtype, device=h.device)
+        return SegPoolFn.apply(ones, h, pb.row_w, pb.mol_row0, pb.mol_nrows)
+
+    def set_rows_atoms(self, atoms):
+        """The pair predictor's hand-over after ``encode_rows``: the LAST step's atom states on the instance rows -- the only
+        step that exists there."""
+        self.atoms_list = [atoms]
+
     def get_atom_array(self, step=-1):
-        """:170-172.  Returns that step's PackedAtoms; ``.dense()`` gives (mb, A, hidden_dim)."""
+        """:170-172.  Returns that step's PackedAtoms; ``.dense()`` gives (mb, A, hidden_dim).  After a call in the encoder
+        layout only the last step (-1 or n_layers - 1) exists."""
         assert len(self.atoms_list) > 0
+        if self._rows_only:
+            if step not in (-1, self.n_layers - 1):
+                raise RuntimeError(f"get_atom_array({step}): " + ROWS_ONLY_REASON)
+            return self.atoms_list[0]
         return self.atoms_list[step]
 
     def get_g_list(self):
         """:174-176: the T readouts readout(h_t, h0, t), each (n_mols, out_dim)."""
+        if self._rows_only:
+            raise RuntimeError("get_g_list(): " + ROWS_ONLY_REASON)
         assert len(self.g_vec_list) > 0
         return self.g_vec_list
 

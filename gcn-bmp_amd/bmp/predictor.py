@@ -50,7 +50,11 @@ class GraphConvPredictorForPair(nn.Module):
             rows0 = None if h0 is None else EncRowsFn.apply(h0, eb)
             # (an encoder with a layer aggregator hands over no atom array: models/ggnn_att.py:648-651)
             at = None if getattr(self.graph_conv, "layer_aggregator", None) else PackedAtoms(rows, eb.pb, None)
-            self.graph_conv.atoms = at
+            hand_over = getattr(self.graph_conv, "set_rows_atoms", None)     # bmp.ggnn_dev.DevGGNN keeps a list of steps
+            if hand_over is not None:
+                hand_over(at)
+            else:
+                self.graph_conv.atoms = at
             g = self.graph_conv.readout_rows(rows, rows0, eb.pb)
             B = eb.pb.side_mols[1]
             return g[:B], g[B:], at, at, (0, B)

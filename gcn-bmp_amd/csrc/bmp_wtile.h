@@ -20,19 +20,23 @@ __device__ __forceinline__ WtWave wt_wave(int tid) {
     return WtWave{tid & 63, w >> 1, w & 1};
 }
 
+// The VAR form of a primitive serves a tile of a tile table (bmp_tile.h: mt_row0 / mt_nblk), whose rows behind its `nrows` =
+// 32 * nblk live rows belong to the next tile or lie past the arrays: no global access goes to a row >= nrows.  Without VAR
+// `nrows` is not read and the code is the whole-tile one.
 // rows [row0, row0 + 128) of the row-major g [.. x D] -> tile [128][D + 4], 16 bytes per lane
-template <int D>
-__device__ __forceinline__ void wt_load_tile(float* tile, const float* __restrict__ g, int row0, int tid) {
-    for (int i = tid; i < WT_R * (D / 4); i += 512) {
+template <int D, bool VAR = false>
+__device__ __forceinline__ void wt_load_tile(float* tile, const float* __restrict__ g, int row0, int tid, int nrows = WT_R) {
+    for (int i = tid; i < (VAR ? nrows : WT_R) * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);
         *(f32x4*)(tile + r * (D + 4) + 4 * q4) = *(const f32x4*)(g + (size_t)(row0 + r) * D + 4 * q4);
     }
 }
 
 // rows [row0, row0 + 128) of the row-major g [.. x ldg], columns [coff, coff + D) := tile, 16 bytes per lane
-template <int D>
-__device__ __forceinline__ void wt_store_tile(const float* tile, float* __restrict__ g, int ldg, int coff, int row0, int tid) {
-    for (int i = tid; i < WT_R * (D / 4); i += 512) {
+template <int D, bool VAR = false>
+__device__ __forceinline__ void wt_store_tile(const float* tile, float* __restrict__ g, int ldg, int coff, int row0, int tid,
+                                              int nrows = WT_R) {
+    for (int i = tid; i < (VAR ? nrows : WT_R) * (D / 4); i += 512) {
         const int r = i / (D / 4), q4 = i % (D / 4);
         *(f32x4*)(g + (size_t)(row0 + r) * ldg + coff + 4 * q4) = *(const f32x4*)(tile + r * (D + 4) + 4 * q4);
     }
@@ -134,11 +138,12 @@ __device__ __forceinline__ void wt_tile_gather(f32x4 (&acc)[D / 16], const float
 }
 
 // ... and filtered by bond type: the sum over the row's entries of type e (col & 3) of val * src[col - row0], no self term.
-// Returns the row's weighted degree for the type (the sum of those entries' values).
-template <int D>
+// Returns the row's weighted degree for the type (the sum of those entries' values).  VAR: called for rows < nrows only (the
+// walk reads ptr[row0 + row + 1]); an entry that points at or behind tile row nrows is skipped.
+template <int D, bool VAR = false>
 __device__ __forceinline__ float wt_tile_gather_typed(f32x4 (&acc)[D / 16], const float* src, int row, int q, int row0,
                                                       const int* __restrict__ ptr, const int* __restrict__ col,
-                                                      const float* __restrict__ val, int e) {
+                                                      const float* __restrict__ val, int e, int nrows = WT_R) {
     constexpr int LD = D + 4, F = D / 16;
 #pragma unroll
     for (int f = 0; f < F; ++f) acc[f] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -147,7 +152,7 @@ __device__ __forceinline__ float wt_tile_gather_typed(f32x4 (&acc)[D / 16], cons
         const int cv = col[ed];
         if ((cv & 3) != e) continue;
         const int j = (cv >> 2) - row0;
-        if ((unsigned)j >= (unsigned)WT_R) continue;          // (molecules never straddle a tile on this path: never taken)
+        if ((unsigned)j >= (unsigned)(VAR ? nrows : WT_R)) continue;      // (molecules never straddle a tile on this path: never taken)
         const float v = val[ed];
         const float* s = src + j * LD + q * (D / 4);
 #pragma unroll

@@ -326,6 +326,23 @@ int bmp_ggnn_loop_step_tile_bwd(const float* dhout, const float* h, const float*
                                 const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* Wnat_p,
                                 const float* Ws_p, const float* A_p, const float* Uc_p, float* dh, float* gda, float* rh,
                                 bmp_stream_t stream);
+/* The same step over a TILE TABLE (csrc/bmp_loop_table.hip), for batches in the encoder layout and the fixed-shape batch: n_tiles
+ * table entries, entry t = rows [mt_row0[t], mt_row0[t] + 32 mt_nblk[t]) with 1..4 live 32-row blocks, one workgroup each; no
+ * molecule straddles an entry; mt_rows = the rows of the arrays.  No row behind an entry's live rows is read or written, and the
+ * waves of a dead block skip their products.  tile_stride: 0 (dense rows) or the table's fixed stride (a multiple of 32, >= 128):
+ * the rows [mt_row0[t] + 32 mt_nblk[t], mt_row0[t] + tile_stride) are then written as ZEROS in every array the call writes (fwd:
+ * hout, m, rz, c; bwd: dh, gda, rh), so that the next step and the weight-gradient calls may read whole arrays.  Everything else
+ * -- operands, the NULL m / rz / c of forward-only evaluation, `first`, the weight-gradient calls -- is as for the _tile_ entries,
+ * and a table of whole tiles at 128 t gives their results bit for bit.  d with bmp_ggnn_loop_step_table_supported (64 or 128). */
+int bmp_ggnn_loop_step_table_supported(int d);
+int bmp_ggnn_loop_step_table_fwd(const float* h, int n_tiles, int d, int first, const int* csr_ptr, const int* csr_col,
+                                 const float* csr_val, const float* WTp, const float* bE, const float* WsTp, const float* bs,
+                                 const float* ATp, const float* UcTp, const float* b, float* m, float* rz, float* c, float* hout,
+                                 const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, bmp_stream_t stream);
+int bmp_ggnn_loop_step_table_bwd(const float* dhout, const float* h, const float* rz, const float* c, int n_tiles, int d, int first,
+                                 const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* Wnat_p,
+                                 const float* Ws_p, const float* A_p, const float* Uc_p, float* dh, float* gda, float* rh,
+                                 const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, bmp_stream_t stream);
 
 /* ---- GGNN step with the edge-network message -- EdgeNetwork, models/ggnn.py:657-720, behind GGNN(message_function=
  * 'edge_network') (csrc/bmp_edge.hip) ----
