@@ -92,6 +92,11 @@ SIGNATURES = {
     "bmp_jk_step_supported": (_I, [_I]),
     "bmp_jk_step_tile_fwd": (_I, [_I, _P, _I, _I] + [_P] * 12),
     "bmp_jk_step_tile_bwd": (_I, [_I, _P, _P, _I, _I] + [_P] * 9),
+    "bmp_jk_step_table_supported": (_I, [_I]),
+    "bmp_jk_step_table_fwd": (_I, [_I, _P, _I, _I] + [_P] * 13 + [_I, _I, _P]),
+    "bmp_jk_step_table_bwd": (_I, [_I, _P, _P, _I, _I] + [_P] * 10 + [_I, _I, _P]),
+    "bmp_jk_mean_fwd": (_I, [_P, _I, _I, _I, _P, _P]),
+    "bmp_jk_mean_bwd": (_I, [_P, _I, _I, _I, _P, _P]),
     "bmp_jk_agg_ws_floats": (_Z, [_I, _I]),
     "bmp_jk_agg_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _P, _Z, _P, _P, _P]),
     "bmp_jk_agg_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _Z, _P, _P]),

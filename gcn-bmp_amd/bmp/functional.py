@@ -1585,11 +1585,18 @@ class PLayerAggFn(Function):
 # whose update is out = relu([h, m] . AU + bU) with no gate -- Nu = d columns (jknet: the whole update) or 2d (jk_gru: the layer
 # in front of its GRU) -- and the parameter-free 'mean' / 'attn' layer aggregators (ggnn_dev_jknet.py:215-226, 297-344).
 # ---------------------------------------------------------------------------------------------------------
-JK_PATHS = {"fused": 0, "composed": 0}           # forward calls per form
+JK_PATHS = {"fused": 0, "composed": 0}           # forward calls per form (a table kernel call counts as fused)
 # (kind, d): the fused step is the default where it beat the composed form by more than the two forms' spreads on the MI355X in at
 # least three of four runs (tools/jk_probe.py, profiles/jk_probe.json); an entry set to False goes through the
 # composed form.  Kind by the update's width: 'jknet' Nu = d, 'jk_gru' Nu = 2d.
 JK_STEP_DEFAULT = {("jknet", 64): True, ("jknet", 128): True, ("jk_gru", 64): True, ("jk_gru", 128): True}
+# On a tile table (the encoder layout, with or without dedup, and the fixed-shape batch): the (kind, d) whose table kernels (csrc/
+# bmp_jk_table.hip) beat the composed form, step forward + backward, by more than the two forms' p90 - median spreads together in
+# at least three of four runs on the 1024-pair DDI-shaped batch in BOTH table layouts (tools/jk_table_probe.py, profiles/
+# jk_table_probe.json); an entry set to False here stays composed on table batches, its kernels reachable through
+# JKStepFn or by setting the entry.  Measured: d = 128 passes for both kinds in 4 of 4 runs in both layouts; d = 64 passes in 4 of 4
+# without dedup and fails with it (jknet 1 of 4, jk_gru 2 of 4: the medians gain 43-107 us per step there, under spreads of 58-110).
+JK_TABLE_DEFAULT = {("jknet", 64): False, ("jknet", 128): True, ("jk_gru", 64): False, ("jk_gru", 128): True}
 JK_AGG_MODE = {"mean": 0, "attn": 1}
 
 
@@ -1597,11 +1604,17 @@ def jk_step_supported(d: int) -> bool:
     return bool(_lib.lib().bmp_jk_step_supported(int(d)))
 
 
+def jk_table_ok(pb, d: int) -> bool:
+    """The batch carries a tile table the jk step's table kernels take (molecules never straddle the table's tiles)."""
+    return pb.mt_row0 is not None and not pb.oversized and bool(_lib.lib().bmp_jk_step_table_supported(int(d)))
+
+
 class JKStepFn(Function):
     """One propagation step -- the GGNN message (plus the self loop h . WsT + bs where WsT is given), then relu([h, m] . AU + bU) --
     as ONE fused kernel per tile and direction.  WT [4d x d], bE [4 x d]: the message weights as MsgFn takes them; WsT [d x d]
     K-major and bs [d], or None for both; AU [2d x Nu] K-major, rows [h-part; m-part], Nu = d or 2d; bU [Nu].  Returns [N x Nu].
-    d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes go through ``jk_step``."""
+    d in {64, 128}, whole tiles (whole_tiles_ok) or a tile table (jk_table_ok: the grid is the table's pb.n_mtiles entries); the
+    other shapes go through ``jk_step``.  The weight gradients are two weight-gradient GEMMs on the kernel's gda either way."""
 
     @staticmethod
     def forward(ctx, h, WT, bE, WsT, bs, AU, bU, pb):
@@ -1614,8 +1627,9 @@ class JKStepFn(Function):
         if nu not in (d, 2 * d) or tuple(WT.shape) != (4 * d, d) or tuple(bE.shape) != (4, d) or tuple(AU.shape) != (2 * d, nu) \
                 or tuple(bU.shape) != (nu,) or (bs is None) == loop or (loop and (tuple(WsT.shape) != (d, d) or tuple(bs.shape) != (d,))):
             raise ValueError("jk step: weight shapes do not match h")
-        if not (whole_tiles_ok(pb) and jk_step_supported(d)):
-            raise ValueError("jk step: the fused kernels take d in {64, 128} on whole tiles; use jk_step()")
+        table = jk_table_ok(pb, d)
+        if not (table or (whole_tiles_ok(pb) and jk_step_supported(d))):
+            raise ValueError("jk step: the fused kernels take d in {64, 128} on whole tiles or on a tile table; use jk_step()")
         bE, bU = bE.contiguous(), bU.contiguous()
         bs = bs.contiguous() if loop else None
         WTp, AUp = pack_k4(WT), pack_k4(AU)
@@ -1623,11 +1637,13 @@ class JKStepFn(Function):
         f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
         infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
         m, out = (None if infer else f(d)), f(nu)
-        check(L.bmp_jk_step_tile_fwd(nu // d, ptr(h), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp),
-                                     ptr(bE), ptr(WsTp), ptr(bs), ptr(AUp), ptr(bU), ptr(m), ptr(out), stream()), "bmp_jk_step_tile_fwd")
+        name = f"bmp_jk_step_{'table' if table else 'tile'}_fwd"
+        check(getattr(L, name)(nu // d, ptr(h), pb.n_mtiles if table else pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col),
+                               ptr(pb.csr_val), ptr(WTp), ptr(bE), ptr(WsTp), ptr(bs), ptr(AUp), ptr(bU), ptr(m), ptr(out),
+                               *_table_args(pb, table), stream()), name)
         if not infer:
             ctx.save_for_backward(h, WT, AU, m, out, WsT if loop else torch.empty(0))
-        ctx.pb, ctx.loop = pb, loop
+        ctx.pb, ctx.loop, ctx.table = pb, loop, table
         JK_PATHS["fused"] += 1
         return out
 
@@ -1635,7 +1651,7 @@ class JKStepFn(Function):
     def backward(ctx, dout):
         L = _lib.lib()
         h, WT, AU, m, out, WsT = ctx.saved_tensors
-        pb, loop = ctx.pb, ctx.loop
+        pb, loop, table = ctx.pb, ctx.loop, ctx.table
         dout = dout.contiguous()
         N, d = h.shape
         nu = AU.shape[1]
@@ -1644,8 +1660,10 @@ class JKStepFn(Function):
         p0 = (5 if loop else 4) * d                                  # gda = [G_0 .. G_3 | dm (self loop) | dpre]
         dh = torch.empty(N, d, dtype=torch.float32, device=h.device)
         gda = torch.empty(N, p0 + nu, dtype=torch.float32, device=h.device)
-        check(L.bmp_jk_step_tile_bwd(nu // d, ptr(dout), ptr(out), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val),
-                                     ptr(Wnat_p), ptr(Ws_p), ptr(Unat_p), ptr(dh), ptr(gda), stream()), "bmp_jk_step_tile_bwd")
+        name = f"bmp_jk_step_{'table' if table else 'tile'}_bwd"
+        check(getattr(L, name)(nu // d, ptr(dout), ptr(out), pb.n_mtiles if table else pb.n_tiles, d, ptr(pb.csrT_ptr),
+                               ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Ws_p), ptr(Unat_p), ptr(dh), ptr(gda),
+                               *_table_args(pb, table), stream()), name)
         o1, cs = _linear_wgrad(h, gda)                               # dWT as [k][e d + c] | dWsT | dAU's h half; all column sums
         o2, _ = _linear_wgrad(m, gda[:, p0:], bias=False)            # dAU's m half
         dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
@@ -1656,11 +1674,14 @@ class JKStepFn(Function):
 def jk_step(h, WT, bE, WsT, bs, AU, bU, pb, fused=True):
     """One step of the jknet (AU 2d x d) / jk_gru (AU 2d x 2d, in front of the GRU) encoders; the weight layouts are JKStepFn's.
     The fused kernels where the tensors are on the GPU, the width is supported (64, 128, and JK_STEP_DEFAULT holds True for it)
-    and no molecule spans tiles; otherwise the existing operators, for any width that is a multiple of 8: the message operator
-    (with its self connection) and the row linear with relu on [h, m].  Both are differentiable through autograd."""
+    and no molecule spans tiles; on a batch with a tile table the table kernels for the (kind, width) JK_TABLE_DEFAULT holds True
+    for; otherwise the existing operators, for any width that is a multiple of 8: the message operator (with its self connection)
+    and the row linear with relu on [h, m].  Both are differentiable through autograd."""
     d = h.shape[1]
     kind = "jknet" if AU.shape[1] == d else "jk_gru"
     if fused and h.is_cuda and whole_tiles_ok(pb) and jk_step_supported(d) and JK_STEP_DEFAULT.get((kind, d), True):
+        return JKStepFn.apply(h, WT, bE, WsT, bs, AU, bU, pb)
+    if fused and h.is_cuda and JK_TABLE_DEFAULT.get((kind, d), False) and jk_table_ok(pb, d):
         return JKStepFn.apply(h, WT, bE, WsT, bs, AU, bU, pb)
     JK_PATHS["composed"] += 1
     m = MsgFn.apply(h, WT, bE, WsT, bs, pb, ACT["identity"])
@@ -1679,7 +1700,9 @@ class JKAggFn(Function):
     """The 'mean' / 'attn' aggregators of models/ggnn_dev_jknet.py:215-226, 297-344 over the step outputs ``hs`` ([N x d] each,
     T <= AGG_MAX_T); ``mode`` from JK_AGG_MODE.  'attn': E_t = <H_t, H_T> + <H_t, H_1> over ALL positions of one batch side (rows
     weighted by row_w, sides = pb.side_tiles), c = softmax_t(E), y = sum_t c_t H_t.  ``coef`` ([n_sides x T], the last call's
-    coefficients) is kept on the Function's context and returned through ``last_coef`` for inspection."""
+    coefficients) is kept on the Function's context and returned through ``last_coef`` for inspection.  On a batch with a tile
+    table (its row count is no multiple of 128, it has no sides to look up) 'mean' runs on the row count (bmp_jk_mean_*) and keeps
+    no coefficients; 'attn' is refused there (bmp.ggnn_jk.JK_ATTN_LAYOUT_REASON)."""
 
     last_coef = None
 
@@ -1698,26 +1721,38 @@ class JKAggFn(Function):
         for t in range(1, T):
             if require_rows(hs[t], f"jk agg: h[{t}]", d).shape[0] != N:
                 raise ValueError("jk aggregator: the step tensors differ in their row count")
-        sides, ns = _jk_side_tiles(pb)
         dev = hs[0].device
         y = torch.empty(N, d, dtype=torch.float32, device=dev)
+        ctx.mode, ctx.pb, ctx.rows = mode, pb, pb.mt_row0 is not None
+        if ctx.rows:
+            if mode != 0:
+                raise ValueError("jk aggregator: 'attn' takes the per-instance batch form (whole tiles per batch side)")
+            check(L.bmp_jk_mean_fwd(_ptr_array(hs), T, N, d, ptr(y), stream()), "bmp_jk_mean_fwd")
+            ctx.save_for_backward(*hs)
+            return y
+        sides, ns = _jk_side_tiles(pb)
         coef = torch.empty(ns, T, dtype=torch.float32, device=dev)
         nws = L.bmp_jk_agg_ws_floats(pb.n_tiles, T)
         ws = _ws(nws, dev)
         check(L.bmp_jk_agg_fwd(_ptr_array(hs), T, pb.n_tiles, d, mode, ptr(pb.row_w), sides, ns, ptr(ws), nws, ptr(coef), ptr(y),
                                stream()), "bmp_jk_agg_fwd")
         ctx.save_for_backward(coef, *hs)
-        ctx.mode, ctx.pb = mode, pb
         JKAggFn.last_coef = coef
         return y
 
     @staticmethod
     def backward(ctx, dy):
         L = _lib.lib()
+        dy = dy.contiguous()
+        if ctx.rows:
+            hs = ctx.saved_tensors
+            N, d = hs[0].shape
+            dhs = [torch.empty_like(hs[0]) for _ in hs]
+            check(L.bmp_jk_mean_bwd(ptr(dy), len(hs), N, d, _ptr_array(dhs), stream()), "bmp_jk_mean_bwd")
+            return (None, None, *dhs)
         coef, *hs = ctx.saved_tensors
         pb, T = ctx.pb, len(hs)
         N, d = hs[0].shape
-        dy = dy.contiguous()
         sides, ns = _jk_side_tiles(pb)
         dhs = [torch.empty_like(hs[0]) for _ in range(T)]
         nws = L.bmp_jk_agg_ws_floats(pb.n_tiles, T)

@@ -12,9 +12,14 @@ Both keep models/ggnn.py's embedding, its message (edge type the fastest axis of
                                              reads the wrong flag);  h' = GRU(2d, d)(x'), stateful: the first call after reset has
                                              no r gate and no U terms, later calls read the GRU's own previous un-dropped output
 
-A step is ``Fn.jk_step``: one fused kernel per tile and direction at hidden_dim 64 / 128 on whole tiles (csrc/bmp_jk.hip), the
-composed operators otherwise (any width that is a multiple of 8, molecules spanning tiles, training dropout); jk_gru's GRU is the
-existing GRU operator on the two d-wide halves of x'.
+A step is ``Fn.jk_step``: one fused kernel per tile and direction at hidden_dim 64 / 128 on whole tiles (csrc/bmp_jk.hip) and,
+for the (kind, width) Fn.JK_TABLE_DEFAULT holds True for, on a tile table -- the encoder layout, dedup, the static batch (csrc/
+bmp_jk_table.hip); the composed operators otherwise (any width that is a multiple of 8, molecules spanning tiles, training
+dropout); jk_gru's GRU is the existing GRU operator on the two d-wide halves of x'.
+
+``encode_rows`` / ``readout_rows`` serve the encoder layout (bmp/enclayout.py) for both classes, without ``concat_hidden``, without
+an active dropout and, for jknet, with every aggregator but 'attn': the arithmetic is per row and per channel then, so a
+molecule's atom states do not depend on its batch side.
 
 The layer aggregators of jknet (select_aggr, :21-42):
     'max'     :201-212, the existing Fn.LayerAggFn in max mode          'mean'  :215-226, y = (1 / T) sum_t h_t
@@ -40,6 +45,7 @@ from torch import nn
 
 from . import functional as Fn
 from .ggnn import GGNN, GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
+from .ggnn_gate import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON
 
 JK_AGGREGATORS = ('concat', 'max', 'mean', 'attn')                  # models/ggnn_dev_jknet.py:23-28, 37-39
 JK_RECURRENT_AGGREGATORS = ('gru', 'bigru')                         # :29-36: refused
@@ -83,8 +89,30 @@ class _JKBase(_StepEncoder):
             cache[li] = message_kernel_weights(self.message_layers[li])
         return cache[li]
 
+    @property
+    def encoder_layout_reason(self):
+        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
+        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
+
+    def rows_reason(self):
+        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
+        if self.layout_reason:
+            return self.layout_reason
+        if self.concat_hidden:
+            return CONCAT_LAYOUT_REASON
+        if self.training and self.dropout_rate != 0.0:
+            return DROPOUT_LAYOUT_REASON
+        return None
+
     def encode_rows(self, pb):
-        raise NotImplementedError("encode_rows: " + (self.layout_reason or "this encoder takes the per-instance batch form"))
+        """The embedding, the steps and, for jknet, the aggregator WITHOUT the readout: (what the readout reads, h0) on the rows of
+        ``pb`` -- the entry the pair predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on
+        the per-instance rows (``readout_rows``)."""
+        reason = self.rows_reason()
+        if reason:
+            raise NotImplementedError("encode_rows: " + reason)
+        _, h0, y, _ = self._encode(pb, None)
+        return y, h0
 
     def get_atom_array(self):
         """Not in the two files: the atom states the readout read (jknet: the aggregated ones), so that the encoders compose with
@@ -128,6 +156,15 @@ class JKNetGGNN(_JKBase):
     def forward(self, atom_array, adj=None):
         """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
         ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
+        pb, h0, y, g_list = self._encode(atom_array, adj)
+        self.atoms = PackedAtoms(y, pb, 0 if pb.dense_map is not None else None)
+        if self.concat_hidden:                                          # :178-179: the aggregator is never called
+            return torch.cat(g_list, dim=1)
+        return self.readout(y, h0, pb, 0)
+
+    def _encode(self, atom_array, adj):
+        """embed + the steps + the aggregator: (pb, h0, what the readout reads [concat_hidden: the last step's states], the
+        per-step readouts of concat_hidden)."""
         pb, h = self._embed(atom_array, adj, "models/ggnn_dev_jknet.py:158-161")
         h0 = h
         drop, masks = self._masks(h)
@@ -142,13 +179,7 @@ class JKNetGGNN(_JKBase):
             if self.concat_hidden:
                 g_list.append(self.readout(h, h0, pb, step))
             hs.append(h)
-        side = 0 if pb.dense_map is not None else None
-        if self.concat_hidden:                                          # :178-179: the aggregator is never called
-            self.atoms = PackedAtoms(h, pb, side)
-            return torch.cat(g_list, dim=1)
-        y = self.aggregate(hs, pb)
-        self.atoms = PackedAtoms(y, pb, side)
-        return self.readout(y, h0, pb, 0)
+        return pb, h0, (h if self.concat_hidden else self.aggregate(hs, pb)), g_list
 
 
 class JKGruGGNN(_JKBase):
@@ -177,6 +208,14 @@ class JKGruGGNN(_JKBase):
     def forward(self, atom_array, adj=None):
         """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
         ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
+        pb, h0, h, g_list = self._encode(atom_array, adj)
+        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+        if self.concat_hidden:
+            return torch.cat(g_list, dim=1)
+        return self.readout(h, h0, pb, 0)
+
+    def _encode(self, atom_array, adj):
+        """embed + the steps: (pb, h0, the last step's states, the per-step readouts of concat_hidden)."""
         pb, h = self._embed(atom_array, adj, "models/ggnn_dev_jk_gru.py:135-138")
         h0 = h
         d = self.hidden_dim
@@ -200,10 +239,7 @@ class JKGruGGNN(_JKBase):
             h = self._dropped(state, step, masks) if drop else state
             if self.concat_hidden:
                 g_list.append(self.readout(h, h0, pb, step))
-        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
-        if self.concat_hidden:
-            return torch.cat(g_list, dim=1)
-        return self.readout(h, h0, pb, 0)
+        return pb, h0, h, g_list
 
 
 class ChinGGNN(GGNN):

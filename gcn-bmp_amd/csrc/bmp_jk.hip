@@ -15,6 +15,7 @@
 //             dm = acc_dm -> the tile X the last product did not read (and into gda with the self loop, acc_dh += X . Ws);
 //             per bond type: G_e = typed transposed-CSR gather(X) -> the other tile (and into gda), acc_dh += it . W_e^T;
 //             dh = acc_dh.      gda [N x ((4 + loop) d + Nu)] = [G_0 .. G_3 | dm (self loop only) | dpre]
+// The two bodies live in bmp_wtile_jk.h: this file instantiates them on whole tiles, bmp_jk_table.hip over a tile table.
 // The weight gradients are the caller's two calls of bmp_linear_wgrad on gda: X = h over all of gda's columns, X = m over its
 // last Nu.  Every term of the backward carries a factor dout: a zero dout row leaves with zero dh and gda rows.
 //
@@ -26,147 +27,7 @@
 // elementwise combine.  No floating-point atomics: two runs add the same numbers in the same order.
 //   backward  dc_t = sum_rows <dy, H_t> (unweighted: the pad row's dy carries its multiplicity);  dE_t = c_t (dc_t - sum_s c_s dc_s);
 //             dH_t = c_t dy + w (dE_t (H_T + H_1) + ([t = T] + [t = 1]) sum_s dE_s H_s)
-#include "bmp_wtile.h"
-
-template <int D, int NG>
-__device__ __forceinline__ void jk_step_fwd(const float* __restrict__ h, const int* __restrict__ ptr, const int* __restrict__ col,
-                                            const float* __restrict__ val, const float* __restrict__ WTp,
-                                            const float* __restrict__ bE, const float* __restrict__ WsTp,
-                                            const float* __restrict__ bs, const float* __restrict__ AUp,
-                                            const float* __restrict__ bU, float* __restrict__ m, float* __restrict__ out) {
-    constexpr int LD = D + 4, NB = D / 64, F = D / 16, NU = NG * D;
-    extern __shared__ float sm[];
-    float* ta = sm;
-    float* tb = sm + WT_R * LD;
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    const int row = tid >> 2, q = tid & 3;                    // the gather's and the bias's (row, quarter) of this thread
-    const int aoff = (wv.b * 32 + (wv.lane & 31)) * LD + 4 * (wv.lane >> 5);          // this lane's A rows in a tile
-    const size_t bcol = wv.ch * NB * 32 + (wv.lane & 31);                             // its first output column
-    wt_load_tile<D>(ta, h, row0, tid);
-    __syncthreads();
-    float wd[4];
-    {
-        f32x16 am[NB];
-        zero_acc(am);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f32x4 g[F];
-            wd[e] = wt_tile_gather_typed<D>(g, ta, row, q, row0, ptr, col, val, e);
-            float* d = tb + row * LD + q * (D / 4);
-#pragma unroll
-            for (int f = 0; f < F; ++f) *(f32x4*)(d + 4 * f) = g[f];
-            __syncthreads();
-            wt_block_mma<NB, false>(am, tb + aoff, WTp + (size_t)e * D * D + ((size_t)(wv.lane >> 5) * D + bcol) * 4, D, D);
-            __syncthreads();
-        }
-        if (WsTp) wt_block_mma<NB, false>(am, ta + aoff, WsTp + ((size_t)(wv.lane >> 5) * D + bcol) * 4, D, D);   // the self loop
-        wt_acc_to_tile<D>(tb, am, wv);
-    }
-    __syncthreads();
-    {   // + sum_e wdeg_e b_e (+ b_s), by the thread that took the row's weighted degrees
-        float* d = tb + row * LD + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) {
-            const int c = q * (D / 4) + 4 * f;
-            f32x4 v = *(const f32x4*)(d + 4 * f);
-            if (WsTp) v += *(const f32x4*)(bs + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v += *(const f32x4*)(bE + e * D + c) * wd[e];
-            *(f32x4*)(d + 4 * f) = v;
-            if (m) *(f32x4*)(m + (size_t)(row0 + row) * D + c) = v;
-        }
-    }
-    __syncthreads();
-    f32x16 au[NG][NB];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) zero_acc(au[g]);
-    const float* Bu = AUp + ((size_t)(wv.lane >> 5) * NU + bcol) * 4;
-    wt_block_mma_g<NG, NB>(au, ta + aoff, Bu, NU, D, D);
-    wt_block_mma_g<NG, NB>(au, tb + aoff, Bu + (size_t)D * NU, NU, D, D);
-    // A wave's products read all d columns of its rows of A and B: nobody writes into A or B before every wave has left them.
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        float* t = (g & 1) ? tb : ta;                         // block 0 -> A, block 1 -> B: one barrier for both
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-            const int c = wt_col(wv, NB, nb);
-            const float bu = bU[g * D + c];
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) t[wt_row(wv, reg) * LD + c] = fmaxf(au[g][nb][reg] + bu, 0.f);
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int g = 0; g < NG; ++g) wt_store_tile<D>((g & 1) ? tb : ta, out, NU, g * D, row0, tid);
-}
-
-template <int D, int NG>
-__device__ __forceinline__ void jk_step_bwd(const float* __restrict__ dout, const float* __restrict__ out,
-                                            const int* __restrict__ ptrT, const int* __restrict__ colT,
-                                            const float* __restrict__ valT, const float* __restrict__ Wnp,
-                                            const float* __restrict__ Wsp, const float* __restrict__ Unp, float* __restrict__ dh,
-                                            float* __restrict__ gda) {
-    constexpr int LD = D + 4, NB = D / 64, F = D / 16, NU = NG * D;
-    extern __shared__ float sm[];
-    float* ta = sm;
-    float* tb = sm + WT_R * LD;
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    const int aoff = (wv.b * 32 + (wv.lane & 31)) * LD + 4 * (wv.lane >> 5);
-    const size_t bcol = wv.ch * NB * 32 + (wv.lane & 31);
-    const int pre0 = (Wsp ? 5 : 4) * D, ldg = pre0 + NU;      // gda's dpre columns and its row stride
-    f32x16 ad[2][NB];                                         // [0]: dh, [1]: dm
-    zero_acc(ad[0]);
-    zero_acc(ad[1]);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-        float* t = (g & 1) ? tb : ta;                         // in turn: the fill of block g + 1 needs no barrier of its own
-        for (int i = tid; i < WT_R * (D / 4); i += 512) {
-            const int r = i / (D / 4), q4 = i % (D / 4);
-            const size_t x = (size_t)(row0 + r) * NU + g * D + 4 * q4;
-            const f32x4 dv = *(const f32x4*)(dout + x), ov = *(const f32x4*)(out + x);
-            f32x4 dp;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dp[j] = ov[j] > 0.f ? dv[j] : 0.f;
-            *(f32x4*)(t + r * LD + 4 * q4) = dp;
-            *(f32x4*)(gda + (size_t)(row0 + r) * ldg + pre0 + g * D + 4 * q4) = dp;
-        }
-        __syncthreads();
-        wt_block_mma_g<2, NB>(ad, t + aoff, Unp + (size_t)g * D * 2 * D + ((size_t)(wv.lane >> 5) * 2 * D + bcol) * 4, 2 * D, D, D);
-    }
-    // dm -> X, the tile the last product did not read: B for one block (nothing read it), A for two (block 0's product read
-    // it, and every wave left that product before the barrier of block 1).  Y, the other tile, is written behind the next barrier.
-    float* tx = (NG & 1) ? tb : ta;
-    float* ty = (NG & 1) ? ta : tb;
-    wt_acc_to_tile<D>(tx, ad[1], wv);
-    __syncthreads();
-    if (Wsp) {                                                // the self loop: dh += dm . Ws, dm into gda
-        wt_block_mma<NB, false>(ad[0], tx + aoff, Wsp + ((size_t)(wv.lane >> 5) * D + bcol) * 4, D, D);
-        wt_store_tile<D>(tx, gda, ldg, 4 * D, row0, tid);
-    }
-    {
-        const int row = tid >> 2, q = tid & 3;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f32x4 g[F];
-            wt_tile_gather_typed<D>(g, tx, row, q, row0, ptrT, colT, valT, e);
-            float* d = ty + row * LD + q * (D / 4);
-            float* gq = gda + (size_t)(row0 + row) * ldg + e * D + q * (D / 4);
-#pragma unroll
-            for (int f = 0; f < F; ++f) { *(f32x4*)(d + 4 * f) = g[f]; *(f32x4*)(gq + 4 * f) = g[f]; }
-            __syncthreads();
-            wt_block_mma<NB, false>(ad[0], ty + aoff, Wnp + ((size_t)(wv.lane >> 5) * 4 * D + e * D + bcol) * 4, 4 * D, D);
-            __syncthreads();
-        }
-    }
-    wt_acc_to_tile<D>(ty, ad[0], wv);                         // (behind the loop's last barrier)
-    __syncthreads();
-    wt_store_tile<D>(ty, dh, D, 0, row0, tid);
-}
+#include "bmp_wtile_jk.h"
 
 #define JK_FWD_ARGS const float* __restrict__ h, const int* __restrict__ ptr, const int* __restrict__ col,                  \
                     const float* __restrict__ val, const float* __restrict__ WTp, const float* __restrict__ bE,              \
@@ -231,14 +92,9 @@ extern "C" int bmp_jk_step_tile_bwd(int ng, const float* dout, const float* out,
 // ---------------------------------------------------------------------------------------------------------
 // 'mean' / 'attn'
 // ---------------------------------------------------------------------------------------------------------
-#define JK_MAXT BMP_AGG_MAXT
 #define JK_MAX_SIDES 4
-#define JK_TPB 256
-#define JK_MAX_BLOCKS 1024
 
 // the T step tensors and the sides' tile boundaries BY VALUE in the kernel arguments (as bmp_agg.hip's AggIn)
-struct JkIn { const float* p[JK_MAXT]; };
-struct JkOut { float* p[JK_MAXT]; };
 struct JkSides { int n; int t[JK_MAX_SIDES + 1]; };           // side s = tiles [t[s], t[s + 1])
 
 __device__ __forceinline__ int jk_side_of(const JkSides& sd, int tile) {
@@ -338,10 +194,7 @@ __global__ __launch_bounds__(JK_TPB) void k_jk_comb(JkIn h, size_t n4, int d, Jk
     const size_t stride = (size_t)gridDim.x * JK_TPB, per_tile = (size_t)WT_R * (d >> 2);
     for (size_t u = (size_t)blockIdx.x * JK_TPB + threadIdx.x; u < n4; u += stride) {
         const float* c = coef + jk_side_of(sd, (int)(u / per_tile)) * T;
-        f32x4 o = reinterpret_cast<const f32x4*>(h.p[0])[u] * c[0];
-#pragma unroll
-        for (int t = 1; t < T; ++t) o += reinterpret_cast<const f32x4*>(h.p[t])[u] * c[t];
-        reinterpret_cast<f32x4*>(y)[u] = o;
+        reinterpret_cast<f32x4*>(y)[u] = jk_comb_unit<T>(h, u, c);
     }
 }
 
@@ -374,23 +227,10 @@ __global__ __launch_bounds__(JK_TPB) void k_jk_agg_bwd(const float* __restrict__
                 reinterpret_cast<f32x4*>(dh.p[t])[u] = g * c[t] + v * w;
             }
         } else {
-#pragma unroll
-            for (int t = 0; t < T; ++t) reinterpret_cast<f32x4*>(dh.p[t])[u] = g * c[t];
+            jk_scale_unit<T>(dh, u, g, c);
         }
     }
 }
-
-static inline int jk_blocks(size_t n4) {
-    const size_t b = (n4 + JK_TPB - 1) / JK_TPB;
-    return (int)(b < 1 ? 1 : (b > JK_MAX_BLOCKS ? JK_MAX_BLOCKS : b));
-}
-
-#define JK_T_SWITCH(T, CASE)                                                                          \
-    switch (T) {                                                                                      \
-        CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)                               \
-        default: return -1000 - __LINE__;                                                             \
-    }
-
 static int jk_sides(const int* side_tiles, int n_sides, int n_tiles, JkSides* sd) {
     BMP_REQUIRE(side_tiles && n_sides >= 1 && n_sides <= JK_MAX_SIDES && side_tiles[0] == 0 && side_tiles[n_sides] == n_tiles);
     sd->n = n_sides;

@@ -130,6 +130,23 @@ extern "C" int bmp_layer_agg_bwd(const float* dy, const float* const* h, int T, 
                                  float* ws, size_t ws_floats, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
+// The jumping-knowledge step over a tile table (bmp_jk_table.hip) and the 'mean' aggregator on a row count (bmp_jk.hip):
+// bmp_jk_step_table_* and bmp_jk_mean_* of include/bmp.h
+// ---------------------------------------------------------------------------------------------
+extern "C" int bmp_jk_step_supported(int d);
+extern "C" int bmp_jk_step_table_supported(int d);
+extern "C" int bmp_jk_step_table_fwd(int ng, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col,
+                                     const float* csr_val, const float* WTp, const float* bE, const float* WsTp, const float* bs,
+                                     const float* AUp, const float* bU, float* m, float* out, const int* mt_row0, const int* mt_nblk,
+                                     int mt_rows, int tile_stride, hipStream_t st);
+extern "C" int bmp_jk_step_table_bwd(int ng, const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr,
+                                     const int* csrT_col, const float* csrT_val, const float* Wnat_p, const float* Ws_p,
+                                     const float* Unat_p, float* dh, float* gda, const int* mt_row0, const int* mt_nblk, int mt_rows,
+                                     int tile_stride, hipStream_t st);
+extern "C" int bmp_jk_mean_fwd(const float* const* h, int T, int n_rows, int d, float* y, hipStream_t st);
+extern "C" int bmp_jk_mean_bwd(const float* dy, int T, int n_rows, int d, float* const* dh, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
 // Optional per-kernel-class timing with HIP events (bench.py's roofline leg).  Off by default;
 // the only process-global state in the library.  While a class is armed, every launch of that
 // class is bracketed by two events on the launch stream.

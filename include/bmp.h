@@ -295,6 +295,25 @@ int bmp_jk_agg_fwd(const float* const* h, int T, int n_tiles, int d, int mode, c
 int bmp_jk_agg_bwd(const float* dy, const float* const* h, int T, int n_tiles, int d, int mode, const float* row_w,
                    const int* side_tiles, int n_sides, const float* coef, float* ws, size_t ws_floats, float* const* dh,
                    bmp_stream_t stream);
+/* The same step over a TILE TABLE (csrc/bmp_jk_table.hip), for batches in the encoder layout and the fixed-shape batch, under the
+ * contract of bmp_ggnn_loop_step_table_*: n_tiles table entries, entry t = rows [mt_row0[t], mt_row0[t] + 32 mt_nblk[t]) with 1..4
+ * live 32-row blocks, one workgroup each; no molecule straddles an entry; mt_rows = the rows of the arrays.  No row behind an
+ * entry's live rows is read or written, and the waves of a dead block skip their products.  tile_stride: 0 (dense rows) or the
+ * table's fixed stride (a multiple of 32, >= 128): the rows [mt_row0[t] + 32 mt_nblk[t], mt_row0[t] + tile_stride) are then
+ * written as ZEROS in every array the call writes (fwd: m, out; bwd: dh, gda).  Everything else is as for the _tile_ entries, and
+ * a table of whole tiles at 128 t gives their results bit for bit.  d with bmp_jk_step_table_supported (64 or 128).
+ * 'mean' on a ROW COUNT (a table batch's rows are no multiple of 128): y [n_rows x d] = (1 / T) sum_t h[t]; bwd: every dh[t] =
+ * dy / T.  T <= 8, d a multiple of 4; no access goes past row n_rows. */
+int bmp_jk_step_table_supported(int d);
+int bmp_jk_step_table_fwd(int ng, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                          const float* WTp, const float* bE, const float* WsTp, const float* bs, const float* AUp, const float* bU,
+                          float* m, float* out, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
+                          bmp_stream_t stream);
+int bmp_jk_step_table_bwd(int ng, const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
+                          const float* csrT_val, const float* Wnat_p, const float* Ws_p, const float* Unat_p, float* dh, float* gda,
+                          const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, bmp_stream_t stream);
+int bmp_jk_mean_fwd(const float* const* h, int T, int n_rows, int d, float* y, bmp_stream_t stream);
+int bmp_jk_mean_bwd(const float* dy, int T, int n_rows, int d, float* const* dh, bmp_stream_t stream);
 
 /* ---- GGNN step with a per-atom self loop in the message -- models/ggnn_dev_self_loop.py:67-110 = models/ggnn_dev_edge.py
  * (csrc/bmp_loop.hip) ----
