@@ -1156,6 +1156,42 @@ def gin_layer(x, W1T, b1, W2T, b2, keep, pb, fused=True):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# The tile-table seam of the step families below (gate, self loop / edge network, jumping knowledge).  A batch is
+# whole 128-row tiles (whole_tiles_ok) or carries a tile table (_table_ok: the encoder layout, with or without dedup, and the
+# fixed-shape batch; entry i is rows [mt_row0[i], mt_row0[i] + 32 mt_nblk[i]), and molecules never straddle the table's tiles).
+# A family's ``*_step`` asks _goes_fused whether a call takes its fused Function; the Function picks the C entry
+# ``..._{tile|table}_{fwd|bwd}`` by name, decides ``table`` once in its forward and keeps it on ctx; a table entry takes
+# pb.n_mtiles for the grid and _table_args behind the whole-tile entry's list.  The weight gradients are _step_wgrad on the
+# kernel's gda either way.
+# ---------------------------------------------------------------------------------------------------------
+def _table_ok(pb) -> bool:
+    return pb.mt_row0 is not None and not pb.oversized
+
+
+def _table_args(pb, table):
+    """The tile-table arguments of a _table_ entry; the whole-tile entries take none."""
+    return [ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride] if table else []
+
+
+def _goes_fused(h, pb, fused, whole, table, state=None) -> bool:
+    """Whether a step call takes its family's fused Function.  ``whole``: the family's kernels take the width and its
+    *_STEP_DEFAULT / GATE_SMALL_DEFAULT entry holds (asked of a batch of whole tiles); ``table``: its *_TABLE_DEFAULT entry holds
+    and its *_table_ok(pb, d).  ``state`` (the GRU's separate state under training dropout) is composed at every width."""
+    return bool(state is None and fused and h.is_cuda and ((whole and whole_tiles_ok(pb)) or table))
+
+
+def _step_wgrad(h, m, gda, p0):
+    """The weight gradients of a fused step from its kernel's gda [N x (p0 + Nu)] = [G_0 .. G_3 | the family's p0 - 4d columns |
+    the update's]: two weight-gradient GEMMs, X = h over all of gda's columns and X = m over those from p0.  Returns dWT [4d x d]
+    in [e*d+k][c] order, the other columns of the h product [d x (p0 - 4d + Nu)], the m product [d x Nu] and all column sums."""
+    d = h.shape[1]
+    o1, cs = _linear_wgrad(h, gda)
+    o2, _ = _linear_wgrad(m, gda[:, p0:], bias=False)
+    dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
+    return dWT, o1[:, 4 * d:], o2, cs
+
+
+# ---------------------------------------------------------------------------------------------------------
 # GGNN step with a fuse gate or a simple gate in the GRU's place (models/ggnn_dev_fuse.py:70-131, models/ggnn_dev_gate.py:73-119;
 # csrc/bmp_gate.hip).
 # ---------------------------------------------------------------------------------------------------------
@@ -1181,8 +1217,8 @@ def gate_step_small_supported(d: int) -> bool:
 
 
 def gate_table_ok(pb, d: int) -> bool:
-    """The batch carries a tile table the d = 32 table kernels take (molecules never straddle the table's tiles)."""
-    return pb.mt_row0 is not None and not pb.oversized and gate_step_small_supported(d)
+    """The batch carries a tile table the d = 32 table kernels take."""
+    return _table_ok(pb) and gate_step_small_supported(d)
 
 
 class GateStepFn(Function):
@@ -1219,19 +1255,14 @@ class GateStepFn(Function):
         f = lambda n: torch.empty(N, n, dtype=torch.float32, device=h.device)
         infer = not any(ctx.needs_input_grad)        # forward-only evaluation: nothing is kept for a backward
         m, act, hout = (None, None, f(d)) if infer else (f(d), f(nu), f(d))
-        if table:
-            check(L.bmp_ggnn_gate_step_small_table_fwd(kind, ptr(h), pb.n_mtiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
-                                                       ptr(WTp), ptr(bE), ptr(AUp), ptr(bU), ptr(keep), ptr(m), ptr(act), ptr(hout),
-                                                       ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride, stream()),
-                  "bmp_ggnn_gate_step_small_table_fwd")
-        else:
-            fwd, name = (L.bmp_ggnn_gate_step_small_fwd, "bmp_ggnn_gate_step_small_fwd") if small else \
-                (L.bmp_ggnn_gate_step_tile_fwd, "bmp_ggnn_gate_step_tile_fwd")
-            check(fwd(kind, ptr(h), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp), ptr(bE), ptr(AUp),
-                      ptr(bU), ptr(keep), ptr(m), ptr(act), ptr(hout), stream()), name)
+        form = "small_table" if table else ("small" if small else "tile")        # the entries' infix
+        name = f"bmp_ggnn_gate_step_{form}_fwd"
+        check(getattr(L, name)(kind, ptr(h), pb.n_mtiles if table else pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                               ptr(WTp), ptr(bE), ptr(AUp), ptr(bU), ptr(keep), ptr(m), ptr(act), ptr(hout), *_table_args(pb, table),
+                               stream()), name)
         if not infer:
             ctx.save_for_backward(h, WT, AU, m, act, keep if keep is not None else torch.empty(0))
-        ctx.pb, ctx.kind, ctx.has_keep = pb, kind, keep is not None
+        ctx.pb, ctx.kind, ctx.has_keep, ctx.form, ctx.table = pb, kind, keep is not None, form, table
         GATE_PATHS["fused"] += 1
         return hout
 
@@ -1239,7 +1270,7 @@ class GateStepFn(Function):
     def backward(ctx, dhout):
         L = _lib.lib()
         h, WT, AU, m, act, keep = ctx.saved_tensors
-        pb, kind = ctx.pb, ctx.kind
+        pb, kind, table = ctx.pb, ctx.kind, ctx.table
         keep = keep if ctx.has_keep else None
         dhout = dhout.contiguous()
         N, d = h.shape
@@ -1247,20 +1278,12 @@ class GateStepFn(Function):
         Wnat_p, Unat_p = pack_k4(WT.t()), pack_k4(AU.t())
         dh = torch.empty(N, d, dtype=torch.float32, device=h.device)
         gda = torch.empty(N, 4 * d + nu, dtype=torch.float32, device=h.device)
-        if gate_table_ok(pb, d):
-            check(L.bmp_ggnn_gate_step_small_table_bwd(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_mtiles, d,
-                                                       ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p),
-                                                       ptr(dh), ptr(gda), ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride,
-                                                       stream()), "bmp_ggnn_gate_step_small_table_bwd")
-        else:
-            bwd, name = (L.bmp_ggnn_gate_step_small_bwd, "bmp_ggnn_gate_step_small_bwd") if gate_step_small_supported(d) else \
-                (L.bmp_ggnn_gate_step_tile_bwd, "bmp_ggnn_gate_step_tile_bwd")
-            check(bwd(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
-                      ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p), ptr(dh), ptr(gda), stream()), name)
-        o1, cs = _linear_wgrad(h, gda)                               # [d x (4d + Nu)]: dWT as [k][e d + c] | dAU's h half; all column sums
-        o2, _ = _linear_wgrad(m, gda[:, 4 * d:], bias=False)         # dAU's m half
-        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
-        return dh, dWT, cs[:4 * d].reshape(4, d), torch.cat((o1[:, 4 * d:], o2), dim=0), cs[4 * d:], None, None, None
+        name = f"bmp_ggnn_gate_step_{ctx.form}_bwd"
+        check(getattr(L, name)(kind, ptr(dhout), ptr(h), ptr(m), ptr(act), ptr(keep), pb.n_mtiles if table else pb.n_tiles, d,
+                               ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Unat_p), ptr(dh), ptr(gda),
+                               *_table_args(pb, table), stream()), name)
+        dWT, dAUh, dAUm, cs = _step_wgrad(h, m, gda, 4 * d)         # gda = [G_0 .. G_3 | the gates']
+        return dh, dWT, cs[:4 * d].reshape(4, d), torch.cat((dAUh, dAUm), dim=0), cs[4 * d:], None, None, None
 
 
 def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
@@ -1273,10 +1296,8 @@ def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
     if kind != 0:
         keep = None
     name = "gate" if kind else "fuse"
-    if fused and h.is_cuda and whole_tiles_ok(pb) and (gate_step_supported(d) or (
-            GATE_SMALL_DEFAULT[name] and gate_step_small_supported(d))):
-        return GateStepFn.apply(h, WT, bE, AU, bU, keep, pb, kind)
-    if fused and h.is_cuda and GATE_TABLE_DEFAULT[name] and gate_table_ok(pb, d):
+    if _goes_fused(h, pb, fused, gate_step_supported(d) or (GATE_SMALL_DEFAULT[name] and gate_step_small_supported(d)),
+                   GATE_TABLE_DEFAULT[name] and gate_table_ok(pb, d)):
         return GateStepFn.apply(h, WT, bE, AU, bU, keep, pb, kind)
     GATE_PATHS["composed"] += 1
     m = MsgFn.apply(h, WT, bE, None, None, pb, ACT["identity"])
@@ -1299,11 +1320,6 @@ def gate_step(h, WT, bE, AU, bU, kind, keep, pb, fused=True):
 def _seg_args(pb, row_mol):
     """The edge entries' segment arguments; the self-loop entries take none (row_mol None)."""
     return [] if row_mol is None else [ptr(pb.row_w), ptr(row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), pb.n_mols]
-
-
-def _table_args(pb, table):
-    """The tile-table arguments of the self loop's _table_ entries; the whole-tile entries take none."""
-    return [ptr(pb.mt_row0), ptr(pb.mt_nblk), pb.n_rows, pb.tile_stride] if table else []
 
 
 def _gru_tile_fwd(ctx, kind, h, WT, W5, AT, UcT, b, pb, first, bE=None, bs=None):
@@ -1357,11 +1373,9 @@ def _gru_tile_bwd(ctx, kind, dhout):
     check(getattr(L, name)(ptr(dhout), ptr(h), ptr(rz), ptr(c), pb.n_mtiles if table else pb.n_tiles, d, first, ptr(pb.csrT_ptr),
                            ptr(pb.csrT_col), ptr(pb.csrT_val), *_seg_args(pb, row_mol[0] if row_mol else None), ptr(Wnat_p), ptr(W5_p),
                            ptr(A_p), ptr(Uc_p), ptr(dh), ptr(gda), ptr(rh), *_table_args(pb, table), stream()), name)
-    o1, cs = _linear_wgrad(h, gda)                               # [d x 8d]: dWT as [k][e d + c] | dW5 | dAT's h half; all column sums
-    o2, _ = _linear_wgrad(m, gda[:, 5 * d:], bias=False)         # dAT's m half
+    dWT, o1, dATm, cs = _step_wgrad(h, m, gda, 5 * d)            # o1 = dW5 | dAT's h half
     dUcT = torch.zeros_like(UcT) if first else _linear_wgrad(rh, gda[:, 7 * d:], bias=False)[0]
-    dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
-    return dh, dWT, o1[:, 4 * d:5 * d], torch.cat((o1[:, 5 * d:], o2), dim=0), dUcT, cs
+    return dh, dWT, o1[:, :d], torch.cat((o1[:, d:], dATm), dim=0), dUcT, cs
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -1382,8 +1396,8 @@ def loop_step_supported(d: int) -> bool:
 
 
 def loop_table_ok(pb, d: int) -> bool:
-    """The batch carries a tile table the self loop's table kernels take (molecules never straddle the table's tiles)."""
-    return pb.mt_row0 is not None and not pb.oversized and bool(_lib.lib().bmp_ggnn_loop_step_table_supported(int(d)))
+    """The batch carries a tile table the self loop's table kernels take."""
+    return _table_ok(pb) and bool(_lib.lib().bmp_ggnn_loop_step_table_supported(int(d)))
 
 
 class LoopStepFn(Function):
@@ -1414,9 +1428,7 @@ def loop_step(h, WT, bE, WsT, bs, AT, UcT, b, first, pb, fused=True, state=None,
     GRU.kernel_weights_state(); training dropout, later calls): the GRU's own un-dropped state, apart from the dropped ``h`` -- the
     separate-state GRU operator, composed at every width (AT, UcT and b are then not read).  Differentiable through autograd."""
     d = h.shape[1]
-    if state is None and fused and h.is_cuda and whole_tiles_ok(pb) and loop_step_supported(d):
-        return LoopStepFn.apply(h, WT, bE, WsT, bs, AT, UcT, b, pb, first)
-    if state is None and fused and h.is_cuda and LOOP_TABLE_DEFAULT.get(d, False) and loop_table_ok(pb, d):
+    if _goes_fused(h, pb, fused, loop_step_supported(d), LOOP_TABLE_DEFAULT.get(d, False) and loop_table_ok(pb, d), state):
         return LoopStepFn.apply(h, WT, bE, WsT, bs, AT, UcT, b, pb, first)
     LOOP_PATHS["composed"] += 1
     m = MsgFn.apply(h, WT, bE, WsT, bs, pb, ACT["identity"])
@@ -1474,7 +1486,7 @@ def edge_step(h, WT, BT, AT, UcT, b, first, pb, fused=True, state=None, state_w=
     state, apart from the dropped ``h`` -- the separate-state GRU operator, composed at every width (AT, UcT and b are then not
     read).  Differentiable through autograd."""
     d = h.shape[1]
-    if state is None and fused and h.is_cuda and whole_tiles_ok(pb) and edge_step_supported(d):
+    if _goes_fused(h, pb, fused, edge_step_supported(d), False, state):
         return EdgeStepFn.apply(h, WT, BT, AT, UcT, b, pb, first)
     from .coarse import RowBcastFn, SegPoolFn
     EDGE_PATHS["composed"] += 1
@@ -1605,8 +1617,8 @@ def jk_step_supported(d: int) -> bool:
 
 
 def jk_table_ok(pb, d: int) -> bool:
-    """The batch carries a tile table the jk step's table kernels take (molecules never straddle the table's tiles)."""
-    return pb.mt_row0 is not None and not pb.oversized and bool(_lib.lib().bmp_jk_step_table_supported(int(d)))
+    """The batch carries a tile table the jk step's table kernels take."""
+    return _table_ok(pb) and bool(_lib.lib().bmp_jk_step_table_supported(int(d)))
 
 
 class JKStepFn(Function):
@@ -1664,11 +1676,9 @@ class JKStepFn(Function):
         check(getattr(L, name)(nu // d, ptr(dout), ptr(out), pb.n_mtiles if table else pb.n_tiles, d, ptr(pb.csrT_ptr),
                                ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(Wnat_p), ptr(Ws_p), ptr(Unat_p), ptr(dh), ptr(gda),
                                *_table_args(pb, table), stream()), name)
-        o1, cs = _linear_wgrad(h, gda)                               # dWT as [k][e d + c] | dWsT | dAU's h half; all column sums
-        o2, _ = _linear_wgrad(m, gda[:, p0:], bias=False)            # dAU's m half
-        dWT = o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)      # [k][e*d+c] -> [e*d+k][c]
-        return (dh, dWT, cs[:4 * d].reshape(4, d), o1[:, 4 * d:p0] if loop else None, cs[4 * d:p0] if loop else None,
-                torch.cat((o1[:, p0:], o2), dim=0), cs[p0:], None)
+        dWT, o1, dAUm, cs = _step_wgrad(h, m, gda, p0)               # o1 = dWsT (self loop) | dAU's h half
+        return (dh, dWT, cs[:4 * d].reshape(4, d), o1[:, :d] if loop else None, cs[4 * d:p0] if loop else None,
+                torch.cat((o1[:, p0 - 4 * d:], dAUm), dim=0), cs[p0:], None)
 
 
 def jk_step(h, WT, bE, WsT, bs, AU, bU, pb, fused=True):
@@ -1679,9 +1689,8 @@ def jk_step(h, WT, bE, WsT, bs, AU, bU, pb, fused=True):
     and the row linear with relu on [h, m].  Both are differentiable through autograd."""
     d = h.shape[1]
     kind = "jknet" if AU.shape[1] == d else "jk_gru"
-    if fused and h.is_cuda and whole_tiles_ok(pb) and jk_step_supported(d) and JK_STEP_DEFAULT.get((kind, d), True):
-        return JKStepFn.apply(h, WT, bE, WsT, bs, AU, bU, pb)
-    if fused and h.is_cuda and JK_TABLE_DEFAULT.get((kind, d), False) and jk_table_ok(pb, d):
+    if _goes_fused(h, pb, fused, jk_step_supported(d) and JK_STEP_DEFAULT.get((kind, d), True),
+                   JK_TABLE_DEFAULT.get((kind, d), False) and jk_table_ok(pb, d)):
         return JKStepFn.apply(h, WT, bE, WsT, bs, AU, bU, pb)
     JK_PATHS["composed"] += 1
     m = MsgFn.apply(h, WT, bE, WsT, bs, pb, ACT["identity"])

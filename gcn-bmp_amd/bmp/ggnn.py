@@ -261,12 +261,25 @@ def as_packed(atom_array, adj, device) -> PackedMolBatch:
     return pack_from_dense([a.astype(np.int32)], [j.astype(np.float32)], device=device)
 
 
+# encode_rows runs an encoder on the encoder layout's rows, where dedup gives all instances of a molecule ONE row set and every
+# tile one shared pad row: an active dropout would give those instances one mask, which is not the per-instance process.
+CONCAT_LAYOUT_REASON = ("concat_hidden=True reads out after every step on the per-instance rows; it takes the per-instance "
+                        "batch form")
+DROPOUT_LAYOUT_REASON = ("dropout_rate > 0 is active in training, and the encoder layout (dedup above all) would give all "
+                         "instances of a molecule one mask; train per-instance or on the static batch, or call eval()")
+
+
 class _StepEncoder(nn.Module):
-    """What the encoders of bmp/ggnn_dev.py and bmp/ggnn_gate.py share: constructor checks, the embedding and message links, the
-    readout links and the readout.  A subclass registers its own links between ``__init__`` and ``_make_readout()``, in its
-    reference file's order (the snapshots map key by key)."""
+    """What the encoders of bmp/ggnn_gate.py, bmp/ggnn_dev.py and bmp/ggnn_jk.py share: constructor checks, the embedding and
+    message links, the readout links and the readout, the embedding of a call's atoms, the training dropout with the masks a test
+    injects, and the rows entry of the encoder layout (``rows_reason`` / ``encode_rows`` / ``readout_rows``, bmp/enclayout.py).  A
+    subclass registers its own links between ``__init__`` and ``_make_readout()``, in its reference file's order (the snapshots
+    map key by key), and supplies ``FLOAT_ATOMS_CITE``, its step loop and ``_rows``."""
 
     NUM_EDGE_TYPE = NUM_EDGE_TYPE
+    FLOAT_ATOMS_CITE = None     # the reference lines of the embedding bypass, named by the float-atom refusal
+    atoms = None                # what the last call's readout read (get_atom_array)
+    layout_reason = None        # why the encoder layout / dedup / the recorded step are refused whatever the mode, if they are
 
     def __init__(self, out_dim, hidden_dim, n_layers, n_atom_types, concat_hidden, dropout_rate, batch_normalization, weight_tying):
         super().__init__()
@@ -301,8 +314,73 @@ class _StepEncoder(nn.Module):
         return Fn.ReadoutFn.apply(h, h0, WT.contiguous(), torch.cat((i.b, j.b)), pb, Fn.ACT["identity"])
 
     def readout_rows(self, h, h0, pb):
-        """The readout of row tensors that live on ``pb``'s rows (the partner of a subclass's ``encode_rows``)."""
+        """The readout of row tensors that live on ``pb``'s rows (the partner of ``encode_rows``)."""
         return self.readout(h, h0, pb, 0)
+
+    def _embed(self, atom_array, adj):
+        """(pb, h): the call's batch -- the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj``
+        is ignored) -- and its embedded atom rows."""
+        if _is_float_atoms(atom_array):
+            raise NotImplementedError(f"float atom features (embedding bypass, {self.FLOAT_ATOMS_CITE}) are not supported")
+        pb = as_packed(atom_array, adj, self.embed.W.device)
+        pb.check_atom_ids(self.embed.W.shape[0])
+        return pb, Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+
+    def _masks(self, h, drop=None):
+        """(drop, masks): ``drop`` (by default: training dropout at ``dropout_rate``), and the masks a test injected for it (one
+        (n_rows, d) tensor per step) or None."""
+        if drop is None:
+            drop = self.dropout_rate != 0.0 and self.training
+        masks = getattr(self, "_dropout_masks", None) if drop else None
+        if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
+            raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
+        return drop, masks
+
+    def _dropped(self, s, step, masks):
+        """chainer's dropout: mask / (1 - ratio)."""
+        return s * masks[step] if masks is not None else torch.nn.functional.dropout(s, p=self.dropout_rate, training=True)
+
+    def _message_weights(self, step, cache):
+        li = 0 if self.weight_tying else step
+        if li not in cache:
+            cache[li] = message_kernel_weights(self.message_layers[li])
+        return cache[li]
+
+    def _packed_atoms(self, h, pb):
+        return PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+
+    def get_atom_array(self):
+        """Not in the reference files (but models/ggnn_dev.py's): the atom states the last call's readout read, so that the
+        encoders compose with every co-attention (as models/ggnn_att.py:662-664 does for the GRU form)."""
+        assert self.atoms is not None
+        return self.atoms
+
+    @property
+    def encoder_layout_reason(self):
+        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
+        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
+
+    def _mode_reason(self):
+        """A class's own reason against ``encode_rows`` in its present mode (between concat_hidden's and the dropout's)."""
+        return None
+
+    def rows_reason(self):
+        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
+        dropout = DROPOUT_LAYOUT_REASON if self.training and self.dropout_rate != 0.0 else None
+        return self.layout_reason or self.encoder_layout_reason or self._mode_reason() or dropout
+
+    def encode_rows(self, pb):
+        """The embedding and the steps WITHOUT the readout: (what the readout reads, h0) on the rows of ``pb`` -- the entry the pair
+        predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the per-instance rows
+        (``readout_rows``)."""
+        reason = self.rows_reason()
+        if reason:
+            raise NotImplementedError("encode_rows: " + reason)
+        return self._rows(pb)
+
+    def _rows(self, pb):
+        """(what the readout reads, h0) of the class's step loop on the rows of ``pb``."""
+        raise NotImplementedError
 
 
 class GGNN(nn.Module):

@@ -14,12 +14,12 @@ reset: no r gate, no U terms) and readout ``sum over ALL positions of sigmoid(i(
                   m = m + h W_s[l]^T + b_s[l], l = 0 if weight_tying else step (:96-97).  Padded positions have no bonds and one
                   h, so m = W_s h + b_s there too and the one virtual pad row per molecule stays exact.  A step is
                   ``Fn.loop_step``: one fused kernel per tile and direction at hidden_dim 64 / 128 on whole tiles
-                  (csrc/bmp_loop.hip) and, for the widths Fn.LOOP_TABLE_DEFAULT holds True for, on a tile table -- the encoder
-                  layout, dedup, the static batch (csrc/bmp_loop_table.hip); the composed operators otherwise.
+                  (csrc/bmp_loop.hip) and, for the widths Fn.LOOP_TABLE_DEFAULT holds True for, on a tile table (csrc/
+                  bmp_loop_table.hip; the tile-table seam of bmp/functional.py); the composed operators otherwise.
 
-``encode_rows`` / ``readout_rows`` serve the encoder layout (bmp/enclayout.py) for both classes, without ``concat_hidden`` and
-without an active dropout.  ``DevGGNN`` keeps only the last step's atom states then: ``get_atom_array()`` / ``get_atom_array(-1)``
-return them, any other step and ``get_g_list()`` raise.
+The rows entry of the encoder layout (``encode_rows`` / ``readout_rows``) is bmp.ggnn._StepEncoder's for both classes.  ``DevGGNN``
+keeps only the last step's atom states then: ``get_atom_array()`` / ``get_atom_array(-1)`` return them, any other step and
+``get_g_list()`` raise.
 
 ``dropout_rate`` (after every step): identity under ``eval()``; in training the step OUTPUT is dropped while the stateful GRU keeps
 its own un-dropped state (the separate-state GRU operator), and the zero-padded positions of a molecule are ONE row of the packed
@@ -36,8 +36,7 @@ from torch import nn
 
 from . import functional as Fn
 from .coarse import SegPoolFn
-from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
-from .ggnn_gate import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON
+from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, _StepEncoder, message_kernel_weights
 
 ROWS_ONLY_REASON = ("the last call ran in the encoder layout, where only the last step's atom states exist on the instance rows; "
                     "per-step outputs need the per-instance batch form")
@@ -46,51 +45,26 @@ ROWS_ONLY_REASON = ("the last call ran in the encoder layout, where only the las
 class _DevBase(_StepEncoder):
     """What the two files share beyond _StepEncoder: the step loop (``_step`` is the subclass's) and the GRU's weights."""
 
+    FLOAT_ATOMS_CITE = "models/ggnn_dev.py:140-143, models/ggnn_dev_self_loop.py:125-128"
+
     def _steps(self, atom_array, adj):
         """embed + the propagation steps: (pb, h0, [h after every step, dropout applied])."""
-        if _is_float_atoms(atom_array):
-            raise NotImplementedError("float atom features (embedding bypass, models/ggnn_dev.py:140-143, "
-                                      "models/ggnn_dev_self_loop.py:125-128) are not supported")
-        pb = as_packed(atom_array, adj, self.embed.W.device)
-        pb.check_atom_ids(self.embed.W.shape[0])
-        h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+        pb, h = self._embed(atom_array, adj)
         h0 = h
-        drop = self.dropout_rate != 0.0 and self.training
-        masks = getattr(self, "_dropout_masks", None) if drop else None      # tests inject the masks (one (n_rows, d) tensor per step)
-        if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
-            raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
+        drop, masks = self._masks(h)
         ctx = dict(pb=pb, drop=drop, state=None, later=None, state_w=None, msgw={}, cache={})
         hs = []
         for step in range(self.n_layers):
             s = self._step(h, step, ctx)
-            if drop:            # the stateful GRU keeps the un-dropped state; chainer's dropout: mask / (1 - ratio)
+            if drop:            # the stateful GRU keeps the un-dropped state
                 ctx["state"] = s
-                h = s * masks[step] if masks is not None else torch.nn.functional.dropout(s, p=self.dropout_rate, training=True)
+                h = self._dropped(s, step, masks)
             else:
                 h = s
             hs.append(h)
         return pb, h0, hs
 
-    @property
-    def encoder_layout_reason(self):
-        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
-        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
-
-    def rows_reason(self):
-        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
-        if self.concat_hidden:
-            return CONCAT_LAYOUT_REASON
-        if self.training and self.dropout_rate != 0.0:
-            return DROPOUT_LAYOUT_REASON
-        return None
-
-    def encode_rows(self, pb):
-        """The embedding and the steps WITHOUT the readout: (h after the last step, h0) on the rows of ``pb`` -- the entry the
-        pair predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the per-instance rows
-        (``readout_rows``)."""
-        reason = self.rows_reason()
-        if reason:
-            raise NotImplementedError("encode_rows: " + reason)
+    def _rows(self, pb):
         _, h0, hs = self._steps(pb, None)
         return hs[-1], h0
 
@@ -126,10 +100,8 @@ class DevGGNN(_DevBase):
 
     def _step(self, h, step, ctx):
         """bmp.ggnn.GGNN.forward's step, without the planned path."""
-        pb, li = ctx["pb"], (0 if self.weight_tying else step)
-        if li not in ctx["msgw"]:
-            ctx["msgw"][li] = message_kernel_weights(self.message_layers[li])
-        WT, bE = ctx["msgw"][li]
+        pb = ctx["pb"]
+        WT, bE = self._message_weights(step, ctx["msgw"])
         AT, UcT, b = self._gru_weights(step, ctx)
         if self.fused and Fn.step_supported(self.hidden_dim) and not ctx["drop"] and not pb.oversized:
             return Fn.GGNNStepFn.apply(h, WT, bE, AT, UcT, b, pb, step == 0, ctx["cache"])
@@ -145,8 +117,7 @@ class DevGGNN(_DevBase):
         self.atoms_list, self.g_vec_list = [], []               # :137-138
         self._rows_only = False
         pb, h0, hs = self._steps(atom_array, adj)
-        side = 0 if pb.dense_map is not None else None
-        self.atoms_list = [PackedAtoms(h, pb, side) for h in hs]
+        self.atoms_list = [self._packed_atoms(h, pb) for h in hs]
         self.g_vec_list = [self.readout(h, h0, pb, t) for t, h in enumerate(hs)]       # :159-160
         if self.concat_hidden:
             return torch.cat(self.g_vec_list, dim=1)            # (:153-155 compute the same readouts a second time)
@@ -159,7 +130,7 @@ class DevGGNN(_DevBase):
         return self.n_layers * self.out_dim if self.concat_hidden else self.hidden_dim
 
     def encode_rows(self, pb):
-        """_DevBase.encode_rows; what the last call kept of its steps is dropped (``set_rows_atoms`` hands over the new atoms)."""
+        """_StepEncoder.encode_rows; what the last call kept of its steps is dropped (``set_rows_atoms`` hands over the new atoms)."""
         self.atoms_list, self.g_vec_list = [], []
         self._rows_only = True
         return super().encode_rows(pb)
@@ -204,7 +175,6 @@ class SelfLoopGGNN(_DevBase):
         self.message_self_loop_layers = nn.ModuleList([Linear(hidden_dim, hidden_dim) for _ in range(self.n_message_layer)])
         self.update_layer = GRU(2 * hidden_dim, hidden_dim)
         self._make_readout()
-        self.atoms = None
 
     def _step(self, h, step, ctx):
         pb, li = ctx["pb"], (0 if self.weight_tying else step)
@@ -220,13 +190,7 @@ class SelfLoopGGNN(_DevBase):
         """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
         ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
         pb, h0, hs = self._steps(atom_array, adj)
-        self.atoms = PackedAtoms(hs[-1], pb, 0 if pb.dense_map is not None else None)
+        self.atoms = self._packed_atoms(hs[-1], pb)
         if self.concat_hidden:
             return torch.cat([self.readout(h, h0, pb, t) for t, h in enumerate(hs)], dim=1)
         return self.readout(hs[-1], h0, pb, 0)
-
-    def get_atom_array(self):
-        """Not in the file: the last step's atom states, so that the encoder composes with every co-attention (as
-        models/ggnn_att.py:662-664 does for the GRU form)."""
-        assert self.atoms is not None
-        return self.atoms

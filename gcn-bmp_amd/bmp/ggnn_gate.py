@@ -12,9 +12,10 @@ Both keep models/ggnn.py's embedding, its message (edge type the fastest axis of
 
 The fuse linears are shared by all steps even when the message weights are untied.  A step is ``Fn.gate_step``: one fused
 kernel per tile and direction at hidden_dim 64 / 128 (csrc/bmp_gate.hip) and at 32, the recorded width (csrc/bmp_gate_small.hip,
-for the kinds Fn.GATE_SMALL_DEFAULT holds True for), on whole tiles; at 32 also on a tile table (the encoder layout, dedup,
-the static batch; Fn.GATE_TABLE_DEFAULT); the composed operators otherwise.  ``encode_rows`` / ``readout_rows`` serve the encoder
-layout: ``GateGGNN`` trains there, ``FuseGGNN`` takes it under ``eval()`` (its training dropout needs per-instance rows).
+for the kinds Fn.GATE_SMALL_DEFAULT holds True for), on whole tiles; at 32 also on a tile table (Fn.GATE_TABLE_DEFAULT; the
+tile-table seam of bmp/functional.py); the composed operators otherwise.  The rows entry of the encoder layout
+(``encode_rows`` / ``readout_rows``) is bmp.ggnn._StepEncoder's: ``GateGGNN`` trains there, ``FuseGGNN`` takes it under ``eval()``
+(its training dropout needs per-instance rows: ``_mode_reason``).
 
 Dropout (the fuse gate's on ``r * h`` and ``dropout_rate`` on every step's output, :157-158): identity under ``eval()``; in
 training the zero-padded positions of a molecule are ONE row of the packed layout and share one mask, where the reference
@@ -31,27 +32,21 @@ import torch
 from torch import nn
 
 from . import functional as Fn
-from .ggnn import GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
+from .ggnn import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON, GRU, Linear, MAX_ATOMIC_NUM, _StepEncoder     # noqa: F401 (the reasons: re-exported)
 
 FUSE_DROPOUT = 0.05             # models/ggnn_dev_fuse.py:127
 
-# encode_rows runs an encoder on the encoder layout's rows, where dedup gives all instances of a molecule ONE row set and every
-# tile one shared pad row: an active dropout would give those instances one mask, which is not the per-instance process.
-CONCAT_LAYOUT_REASON = ("concat_hidden=True reads out after every step on the per-instance rows; it takes the per-instance "
-                        "batch form")
 FUSE_TRAIN_LAYOUT_REASON = ("the fuse gate's dropout on r * h is active in training, and the encoder layout (dedup above all) "
                             "would give all instances of a molecule one mask; train per-instance or on the static batch, or call "
                             "eval()")
-DROPOUT_LAYOUT_REASON = ("dropout_rate > 0 is active in training, and the encoder layout (dedup above all) would give all "
-                         "instances of a molecule one mask; train per-instance or on the static batch, or call eval()")
 
 
 class _GatedGGNN(_StepEncoder):
     """What the two files share beyond _StepEncoder (its readout is :133-141): the step loop."""
 
+    FLOAT_ATOMS_CITE = "models/ggnn_dev_fuse.py:149-150, models/ggnn_dev_gate.py:136-137"
     KIND = None                 # Fn.GATE_KIND of the subclass
     _fused = True               # private switch: False takes the composed operators at every width (32, 64 and 128 included)
-    atoms = None                # the last call's atom states (get_atom_array)
 
     def _update_weights(self, step):
         """(AU [2d x Nu], bU [Nu]) of the step, in Fn.gate_step's layout."""
@@ -60,33 +55,22 @@ class _GatedGGNN(_StepEncoder):
     def forward(self, atom_array, adj=None):
         """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
         ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
-        if _is_float_atoms(atom_array):
-            raise NotImplementedError("float atom features (embedding bypass, models/ggnn_dev_fuse.py:149-150, "
-                                      "models/ggnn_dev_gate.py:136-137) are not supported")
-        pb = as_packed(atom_array, adj, self.embed.W.device)
         g_list = [] if self.concat_hidden else None
-        h, h0 = self._steps(pb, g_list)
-        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
+        pb, h, h0 = self._steps(atom_array, adj, g_list)
+        self.atoms = self._packed_atoms(h, pb)
         if self.concat_hidden:
             return torch.cat(g_list, dim=1)
         return self.readout(h, h0, pb, 0)
 
-    def _steps(self, pb, g_list=None):
-        """The embedding and the propagation steps on the rows of ``pb``: (h, h0).  ``g_list`` collects the per-step readouts of
-        concat_hidden."""
-        pb.check_atom_ids(self.embed.W.shape[0])
-        h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+    def _steps(self, atom_array, adj=None, g_list=None):
+        """The embedding and the propagation steps: (pb, h, h0).  ``g_list`` collects the per-step readouts of concat_hidden."""
+        pb, h = self._embed(atom_array, adj)
         h0 = h
         fuse = self.KIND == Fn.GATE_KIND["fuse"]
         # (tests inject the fuse gate's training masks: one (n_rows, hidden) tensor per step)
-        masks = getattr(self, "_dropout_masks", None) if (self.training and fuse) else None
-        if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
-            raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
+        _, masks = self._masks(h, self.training and fuse)
         msgw, updw = {}, {}
         for step in range(self.n_layers):
-            li = 0 if self.weight_tying else step
-            if li not in msgw:
-                msgw[li] = message_kernel_weights(self.message_layers[li])
             ui = self._update_index(step)
             if ui not in updw:
                 updw[ui] = self._update_weights(ui)
@@ -96,50 +80,27 @@ class _GatedGGNN(_StepEncoder):
                     keep = masks[step]
                 else:
                     keep = (torch.rand(h.shape, device=h.device) >= FUSE_DROPOUT).to(torch.float32) * (1.0 / (1.0 - FUSE_DROPOUT))
-            h = Fn.gate_step(h, *msgw[li], *updw[ui], self.KIND, keep, pb, self._fused)
-            if self.dropout_rate != 0.0 and self.training:              # :157-158, chainer: mask / (1 - ratio)
-                h = torch.nn.functional.dropout(h, p=self.dropout_rate, training=True)
+            h = Fn.gate_step(h, *self._message_weights(step, msgw), *updw[ui], self.KIND, keep, pb, self._fused)
+            if self.dropout_rate != 0.0 and self.training:              # :157-158
+                h = self._dropped(h, step, None)
             if g_list is not None:
                 g_list.append(self.readout(h, h0, pb, step))
-        return h, h0
+        return pb, h, h0
 
-    @property
-    def encoder_layout_reason(self):
-        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
-        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
-
-    def rows_reason(self):
-        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
-        if self.concat_hidden:
-            return CONCAT_LAYOUT_REASON
-        if self.training and self.KIND == Fn.GATE_KIND["fuse"]:
-            return FUSE_TRAIN_LAYOUT_REASON
-        if self.training and self.dropout_rate != 0.0:
-            return DROPOUT_LAYOUT_REASON
-        return None
-
-    def encode_rows(self, pb):
-        """The embedding and the steps WITHOUT the readout: (h, h0) on the rows of ``pb`` -- the entry the pair predictor uses
-        for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the per-instance rows (``readout_rows``)."""
-        reason = self.rows_reason()
-        if reason:
-            raise NotImplementedError("encode_rows: " + reason)
-        return self._steps(pb)
+    def _rows(self, pb):
+        return self._steps(pb)[1:]
 
     def _update_index(self, step):
         return 0
-
-    def get_atom_array(self):
-        """Not in the two files: the last step's atom states, so that the encoders compose with every co-attention (as
-        models/ggnn_att.py:662-664 does for the GRU form)."""
-        assert self.atoms is not None
-        return self.atoms
 
 
 class FuseGGNN(_GatedGGNN):
     """models/ggnn_dev_fuse.py:18-168."""
 
     KIND = Fn.GATE_KIND["fuse"]
+
+    def _mode_reason(self):
+        return FUSE_TRAIN_LAYOUT_REASON if self.training else None
 
     def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
                  batch_normalization=False, weight_tying=True):

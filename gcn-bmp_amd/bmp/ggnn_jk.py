@@ -13,12 +13,12 @@ Both keep models/ggnn.py's embedding, its message (edge type the fastest axis of
                                              no r gate and no U terms, later calls read the GRU's own previous un-dropped output
 
 A step is ``Fn.jk_step``: one fused kernel per tile and direction at hidden_dim 64 / 128 on whole tiles (csrc/bmp_jk.hip) and,
-for the (kind, width) Fn.JK_TABLE_DEFAULT holds True for, on a tile table -- the encoder layout, dedup, the static batch (csrc/
-bmp_jk_table.hip); the composed operators otherwise (any width that is a multiple of 8, molecules spanning tiles, training
-dropout); jk_gru's GRU is the existing GRU operator on the two d-wide halves of x'.
+for the (kind, width) Fn.JK_TABLE_DEFAULT holds True for, on a tile table (csrc/bmp_jk_table.hip; the tile-table seam of bmp/
+functional.py); the composed operators otherwise (any width that is a multiple of 8, molecules spanning tiles,
+training dropout); jk_gru's GRU is the existing GRU operator on the two d-wide halves of x'.
 
-``encode_rows`` / ``readout_rows`` serve the encoder layout (bmp/enclayout.py) for both classes, without ``concat_hidden``, without
-an active dropout and, for jknet, with every aggregator but 'attn': the arithmetic is per row and per channel then, so a
+The rows entry of the encoder layout (``encode_rows`` / ``readout_rows``) is bmp.ggnn._StepEncoder's for both classes; jknet's runs
+the aggregator too, and takes every aggregator but 'attn' (``layout_reason``): the arithmetic is per row and per channel then, so a
 molecule's atom states do not depend on its batch side.
 
 The layer aggregators of jknet (select_aggr, :21-42):
@@ -44,8 +44,7 @@ import torch
 from torch import nn
 
 from . import functional as Fn
-from .ggnn import GGNN, GRU, Linear, MAX_ATOMIC_NUM, PackedAtoms, _StepEncoder, _is_float_atoms, as_packed, message_kernel_weights
-from .ggnn_gate import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON
+from .ggnn import GGNN, GRU, Linear, MAX_ATOMIC_NUM, _StepEncoder
 
 JK_AGGREGATORS = ('concat', 'max', 'mean', 'attn')                  # models/ggnn_dev_jknet.py:23-28, 37-39
 JK_RECURRENT_AGGREGATORS = ('gru', 'bigru')                         # :29-36: refused
@@ -58,71 +57,29 @@ JK_ATTN_LAYOUT_REASON = (
 
 
 class _JKBase(_StepEncoder):
-    """What the two files share beyond _StepEncoder: embed, the step loop with its dropout, the atom array."""
+    """What the two files share beyond _StepEncoder: the call and the rows entry over the subclass's ``_encode``."""
 
     _fused = True               # private switch: False takes the composed operators at every width
-    atoms = None                # what the last call's readout read (get_atom_array)
-    layout_reason = None        # why the encoder layout / dedup / the recorded step are refused, if they are
 
-    def _embed(self, atom_array, adj, cite):
-        if _is_float_atoms(atom_array):
-            raise NotImplementedError(f"float atom features (embedding bypass, {cite}) are not supported")
-        pb = as_packed(atom_array, adj, self.embed.W.device)
-        pb.check_atom_ids(self.embed.W.shape[0])
-        return pb, Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+    def forward(self, atom_array, adj=None):
+        """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
+        ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
+        pb, h0, y, g_list = self._encode(atom_array, adj)
+        self.atoms = self._packed_atoms(y, pb)                          # (jknet: the aggregated states)
+        if self.concat_hidden:                                          # (jknet :178-179: the aggregator is never called)
+            return torch.cat(g_list, dim=1)
+        return self.readout(y, h0, pb, 0)
 
-    def _masks(self, h):
-        """(drop, masks): training dropout, and the masks a test injected (one (n_rows, d) tensor per step) or None."""
-        drop = self.dropout_rate != 0.0 and self.training
-        masks = getattr(self, "_dropout_masks", None) if drop else None
-        if masks is not None and (len(masks) != self.n_layers or any(tuple(k.shape) != tuple(h.shape) for k in masks)):
-            raise ValueError(f"_dropout_masks: expected {self.n_layers} tensors of shape {tuple(h.shape)}")
-        return drop, masks
-
-    def _dropped(self, s, step, masks):
-        """chainer's dropout: mask / (1 - ratio)."""
-        return s * masks[step] if masks is not None else torch.nn.functional.dropout(s, p=self.dropout_rate, training=True)
-
-    def _message_weights(self, step, cache):
-        li = 0 if self.weight_tying else step
-        if li not in cache:
-            cache[li] = message_kernel_weights(self.message_layers[li])
-        return cache[li]
-
-    @property
-    def encoder_layout_reason(self):
-        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder)."""
-        return CONCAT_LAYOUT_REASON if self.concat_hidden else None
-
-    def rows_reason(self):
-        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs."""
-        if self.layout_reason:
-            return self.layout_reason
-        if self.concat_hidden:
-            return CONCAT_LAYOUT_REASON
-        if self.training and self.dropout_rate != 0.0:
-            return DROPOUT_LAYOUT_REASON
-        return None
-
-    def encode_rows(self, pb):
-        """The embedding, the steps and, for jknet, the aggregator WITHOUT the readout: (what the readout reads, h0) on the rows of
-        ``pb`` -- the entry the pair predictor uses for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on
-        the per-instance rows (``readout_rows``)."""
-        reason = self.rows_reason()
-        if reason:
-            raise NotImplementedError("encode_rows: " + reason)
+    def _rows(self, pb):
+        """(jknet: the aggregator's output too, without the readout.)"""
         _, h0, y, _ = self._encode(pb, None)
         return y, h0
-
-    def get_atom_array(self):
-        """Not in the two files: the atom states the readout read (jknet: the aggregated ones), so that the encoders compose with
-        every co-attention (as models/ggnn_att.py:662-664 does for the GRU form)."""
-        assert self.atoms is not None
-        return self.atoms
 
 
 class JKNetGGNN(_JKBase):
     """models/ggnn_dev_jknet.py:45-186."""
+
+    FLOAT_ATOMS_CITE = "models/ggnn_dev_jknet.py:158-161"
 
     def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
                  layer_aggr=None, batch_normalization=False, weight_tying=True, update_tying=True):
@@ -153,19 +110,10 @@ class JKNetGGNN(_JKBase):
             return Fn.LayerAggFn.apply(Fn.AGG_MODE["max-pool"], None, None, *hs)
         return Fn.JKAggFn.apply(Fn.JK_AGG_MODE[self.layer_aggr], pb, *hs)
 
-    def forward(self, atom_array, adj=None):
-        """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
-        ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
-        pb, h0, y, g_list = self._encode(atom_array, adj)
-        self.atoms = PackedAtoms(y, pb, 0 if pb.dense_map is not None else None)
-        if self.concat_hidden:                                          # :178-179: the aggregator is never called
-            return torch.cat(g_list, dim=1)
-        return self.readout(y, h0, pb, 0)
-
     def _encode(self, atom_array, adj):
         """embed + the steps + the aggregator: (pb, h0, what the readout reads [concat_hidden: the last step's states], the
         per-step readouts of concat_hidden)."""
-        pb, h = self._embed(atom_array, adj, "models/ggnn_dev_jknet.py:158-161")
+        pb, h = self._embed(atom_array, adj)
         h0 = h
         drop, masks = self._masks(h)
         msgw, updw, hs, g_list = {}, {}, [], []
@@ -184,6 +132,8 @@ class JKNetGGNN(_JKBase):
 
 class JKGruGGNN(_JKBase):
     """models/ggnn_dev_jk_gru.py:20-155."""
+
+    FLOAT_ATOMS_CITE = "models/ggnn_dev_jk_gru.py:135-138"
 
     def __init__(self, out_dim, hidden_dim=16, n_layers=4, n_atom_types=MAX_ATOMIC_NUM, concat_hidden=False, dropout_rate=0.0,
                  batch_normalization=False, weight_tying=True, update_tying=True, self_loop=False):
@@ -205,18 +155,9 @@ class JKGruGGNN(_JKBase):
             self.self_loop_layer = Linear(hidden_dim, hidden_dim)       # :61-62: ONE layer, not one per message layer
         self._make_readout()
 
-    def forward(self, atom_array, adj=None):
-        """``atom_array`` is the dense int32 (mb, A) array with ``adj`` (mb, 4, A, A), or a PackedMolBatch (then ``adj`` is
-        ignored).  Returns (n_mols, out_dim) [(n_mols, n_layers * out_dim) with concat_hidden]."""
-        pb, h0, h, g_list = self._encode(atom_array, adj)
-        self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
-        if self.concat_hidden:
-            return torch.cat(g_list, dim=1)
-        return self.readout(h, h0, pb, 0)
-
     def _encode(self, atom_array, adj):
         """embed + the steps: (pb, h0, the last step's states, the per-step readouts of concat_hidden)."""
-        pb, h = self._embed(atom_array, adj, "models/ggnn_dev_jk_gru.py:135-138")
+        pb, h = self._embed(atom_array, adj)
         h0 = h
         d = self.hidden_dim
         drop, masks = self._masks(h)

@@ -52,6 +52,12 @@ inline int bmp_lds_attr(const void* fn, size_t bytes) {
         if (!(cond)) return -1000 - __LINE__;                     \
     } while (0)
 
+// What every _table_ step entry asks of its tile table: both arrays, rows in them, and a fixed stride (0: dense rows) that is
+// whole 32-row blocks and holds the tallest tile (tile_rows rows).
+static inline bool bmp_tile_table_ok(const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, int tile_rows) {
+    return mt_row0 && mt_nblk && mt_rows > 0 && (tile_stride == 0 || (tile_stride >= tile_rows && tile_stride % 32 == 0));
+}
+
 // MFMA 32x32x2 f32 fragment maps (cdna guide section 3):
 //   A operand: lane l holds A[i = l & 31][k = l >> 5]
 //   B operand: lane l holds B[k = l >> 5][j = l & 31]

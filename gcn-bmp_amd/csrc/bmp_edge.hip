@@ -45,11 +45,8 @@ extern "C" int bmp_ggnn_edge_step_tile_fwd(const float* h, int n_tiles, int d, i
                                            const int* mol_nrows, int n_mols, const float* WTp, const float* BTp, const float* ATp,
                                            const float* UcTp, const float* b, float* m, float* rz, float* c, float* hout,
                                            hipStream_t st) {
-    BMP_REQUIRE(h && n_tiles > 0 && bmp_ggnn_edge_step_supported(d) && csr_ptr && WTp && BTp && ATp && b && hout);
     BMP_REQUIRE(row_w && row_mol && mol_row0 && mol_nrows && n_mols > 0);
-    BMP_REQUIRE((first || UcTp) && (m == nullptr) == (rz == nullptr) && (m == nullptr) == (c == nullptr));
-    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WTp | (uintptr_t)BTp | (uintptr_t)ATp | (uintptr_t)UcTp | (uintptr_t)m | (uintptr_t)rz |
-                  (uintptr_t)c | (uintptr_t)hout) & 15) == 0);
+    if (int rc = wg_fwd_check(bmp_ggnn_edge_step_supported(d), h, n_tiles, first, csr_ptr, WTp, BTp, ATp, UcTp, b, m, rz, c, hout)) return rc;
     const EdgeSeg sg{row_w, row_mol, mol_row0, mol_nrows, n_mols};
     if (first)
         WT_LAUNCH(k_edge_step_first_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, sg, WTp, BTp, ATp, UcTp, b, m, rz, c, hout);
@@ -65,11 +62,8 @@ extern "C" int bmp_ggnn_edge_step_tile_bwd(const float* dhout, const float* h, c
                                            const float* row_w, const int* row_mol, const int* mol_row0, const int* mol_nrows,
                                            int n_mols, const float* Wnat_p, const float* B_p, const float* A_p, const float* Uc_p,
                                            float* dh, float* gda, float* rh, hipStream_t st) {
-    BMP_REQUIRE(dhout && h && rz && c && n_tiles > 0 && bmp_ggnn_edge_step_supported(d) && csrT_ptr && Wnat_p && B_p && A_p && dh && gda);
     BMP_REQUIRE(row_w && row_mol && mol_row0 && mol_nrows && n_mols > 0);
-    BMP_REQUIRE(first || (Uc_p && rh));
-    BMP_REQUIRE((((uintptr_t)dhout | (uintptr_t)h | (uintptr_t)rz | (uintptr_t)c | (uintptr_t)Wnat_p | (uintptr_t)B_p | (uintptr_t)A_p |
-                  (uintptr_t)Uc_p | (uintptr_t)dh | (uintptr_t)gda | (uintptr_t)rh) & 15) == 0);
+    if (int rc = wg_bwd_check(bmp_ggnn_edge_step_supported(d), dhout, h, rz, c, n_tiles, first, csrT_ptr, Wnat_p, B_p, A_p, Uc_p, dh, gda, rh)) return rc;
     const EdgeSeg sg{row_w, row_mol, mol_row0, mol_nrows, n_mols};
     if (first)
         WT_LAUNCH(k_edge_step_first_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dhout, h, rz, c, csrT_ptr, csrT_col, csrT_val, sg, Wnat_p, B_p, A_p, Uc_p, dh, gda, rh);

@@ -53,8 +53,6 @@ __global__ __launch_bounds__(512) void k_jk_step2_tile_bwd(JK_BWD_ARGS) {
     jk_step_bwd<D, 2>(dout, out, ptrT, colT, valT, Wnp, Wsp, Unp, dh, gda);
 }
 
-static inline bool jk_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 extern "C" int bmp_jk_step_supported(int d) { return d == 64 || d == 128; }
 
 // ng 1 / 2: Nu = ng d.  WTp [4d x d], bE [4 x d]: the message weight as bmp_ggnn_step_fwd takes it; WsTp [d x d] K-major, K4-packed,
@@ -63,10 +61,7 @@ extern "C" int bmp_jk_step_supported(int d) { return d == 64 || d == 128; }
 extern "C" int bmp_jk_step_tile_fwd(int ng, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col,
                                     const float* csr_val, const float* WTp, const float* bE, const float* WsTp, const float* bs,
                                     const float* AUp, const float* bU, float* m, float* out, hipStream_t st) {
-    BMP_REQUIRE((ng == 1 || ng == 2) && h && n_tiles > 0 && bmp_jk_step_supported(d));
-    BMP_REQUIRE(csr_ptr && WTp && bE && AUp && bU && out && (WsTp == nullptr) == (bs == nullptr));
-    BMP_REQUIRE(jk_aligned(h) && jk_aligned(WTp) && jk_aligned(bE) && jk_aligned(WsTp) && jk_aligned(bs) && jk_aligned(AUp) &&
-                jk_aligned(m) && jk_aligned(out));
+    if (int rc = jk_fwd_check(bmp_jk_step_supported(d), ng, h, n_tiles, csr_ptr, WTp, bE, WsTp, bs, AUp, bU, m, out)) return rc;
     if (ng == 1)
         WT_LAUNCH(k_jk_step1_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, WTp, bE, WsTp, bs, AUp, bU, m, out);
     else
@@ -78,10 +73,7 @@ extern "C" int bmp_jk_step_tile_fwd(int ng, const float* h, int n_tiles, int d, 
 extern "C" int bmp_jk_step_tile_bwd(int ng, const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr,
                                     const int* csrT_col, const float* csrT_val, const float* Wnat_p, const float* Ws_p,
                                     const float* Unat_p, float* dh, float* gda, hipStream_t st) {
-    BMP_REQUIRE((ng == 1 || ng == 2) && dout && out && n_tiles > 0 && bmp_jk_step_supported(d));
-    BMP_REQUIRE(csrT_ptr && Wnat_p && Unat_p && dh && gda);
-    BMP_REQUIRE(jk_aligned(dout) && jk_aligned(out) && jk_aligned(Wnat_p) && jk_aligned(Ws_p) && jk_aligned(Unat_p) && jk_aligned(dh) &&
-                jk_aligned(gda));
+    if (int rc = jk_bwd_check(bmp_jk_step_supported(d), ng, dout, out, n_tiles, csrT_ptr, Wnat_p, Ws_p, Unat_p, dh, gda)) return rc;
     if (ng == 1)
         WT_LAUNCH(k_jk_step1_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dout, out, csrT_ptr, csrT_col, csrT_val, Wnat_p, Ws_p, Unat_p, dh, gda);
     else

@@ -30,23 +30,14 @@ template <int D> __global__ __launch_bounds__(512) void k_jk_step2_table_bwd(JKT
 
 extern "C" int bmp_jk_step_table_supported(int d) { return bmp_jk_step_supported(d); }
 
-// a tile table is both arrays, and a fixed stride (0: dense rows) is whole 32-row blocks and holds the tallest tile
-static bool jk_table_ok(const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride) {
-    return mt_row0 && mt_nblk && mt_rows > 0 && (tile_stride == 0 || (tile_stride >= WT_R && tile_stride % 32 == 0));
-}
-static inline bool jkt_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // bmp_jk_step_tile_fwd over a tile table: n_tiles table entries, mt_rows rows in the arrays; tile_stride 0 (dense rows) or the
 // fixed stride of the table's tiles, whose dead rows are then cleared in m and out.
 extern "C" int bmp_jk_step_table_fwd(int ng, const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col,
                                      const float* csr_val, const float* WTp, const float* bE, const float* WsTp, const float* bs,
                                      const float* AUp, const float* bU, float* m, float* out, const int* mt_row0, const int* mt_nblk,
                                      int mt_rows, int tile_stride, hipStream_t st) {
-    BMP_REQUIRE(jk_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride));
-    BMP_REQUIRE((ng == 1 || ng == 2) && h && n_tiles > 0 && bmp_jk_step_table_supported(d));
-    BMP_REQUIRE(csr_ptr && WTp && bE && AUp && bU && out && (WsTp == nullptr) == (bs == nullptr));
-    BMP_REQUIRE(jkt_aligned(h) && jkt_aligned(WTp) && jkt_aligned(bE) && jkt_aligned(WsTp) && jkt_aligned(bs) && jkt_aligned(AUp) &&
-                jkt_aligned(m) && jkt_aligned(out));
+    BMP_REQUIRE(bmp_tile_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride, WT_R));
+    if (int rc = jk_fwd_check(bmp_jk_step_table_supported(d), ng, h, n_tiles, csr_ptr, WTp, bE, WsTp, bs, AUp, bU, m, out)) return rc;
     const WgTable tt = {mt_row0, mt_nblk, mt_rows, tile_stride};
     if (ng == 1)
         WT_LAUNCH(k_jk_step1_table_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, WTp, bE, WsTp, bs, AUp, bU, m, out, tt);
@@ -60,11 +51,8 @@ extern "C" int bmp_jk_step_table_bwd(int ng, const float* dout, const float* out
                                      const int* csrT_col, const float* csrT_val, const float* Wnat_p, const float* Ws_p,
                                      const float* Unat_p, float* dh, float* gda, const int* mt_row0, const int* mt_nblk, int mt_rows,
                                      int tile_stride, hipStream_t st) {
-    BMP_REQUIRE(jk_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride));
-    BMP_REQUIRE((ng == 1 || ng == 2) && dout && out && n_tiles > 0 && bmp_jk_step_table_supported(d));
-    BMP_REQUIRE(csrT_ptr && Wnat_p && Unat_p && dh && gda);
-    BMP_REQUIRE(jkt_aligned(dout) && jkt_aligned(out) && jkt_aligned(Wnat_p) && jkt_aligned(Ws_p) && jkt_aligned(Unat_p) &&
-                jkt_aligned(dh) && jkt_aligned(gda));
+    BMP_REQUIRE(bmp_tile_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride, WT_R));
+    if (int rc = jk_bwd_check(bmp_jk_step_table_supported(d), ng, dout, out, n_tiles, csrT_ptr, Wnat_p, Ws_p, Unat_p, dh, gda)) return rc;
     const WgTable tt = {mt_row0, mt_nblk, mt_rows, tile_stride};
     if (ng == 1)
         WT_LAUNCH(k_jk_step1_table_bwd, d, n_tiles, wt_lds_bytes(d), st, dout, out, csrT_ptr, csrT_col, csrT_val, Wnat_p, Ws_p, Unat_p, dh, gda, tt);
@@ -97,10 +85,10 @@ __global__ __launch_bounds__(JK_TPB) void k_jk_mean_bwd(const float* __restrict_
 // 'mean' on a row count: h, T host pointers to the step outputs [n_rows x d]; y [n_rows x d] = (1 / T) sum_t h[t].  No access
 // goes past row n_rows.
 extern "C" int bmp_jk_mean_fwd(const float* const* h, int T, int n_rows, int d, float* y, hipStream_t st) {
-    BMP_REQUIRE(h && T >= 1 && T <= JK_MAXT && n_rows > 0 && d > 0 && d % 4 == 0 && y && jkt_aligned(y));
+    BMP_REQUIRE(h && T >= 1 && T <= JK_MAXT && n_rows > 0 && d > 0 && d % 4 == 0 && y && jk_aligned(y));
     JkIn in = {};
     for (int t = 0; t < T; ++t) {
-        BMP_REQUIRE(h[t] && jkt_aligned(h[t]));
+        BMP_REQUIRE(h[t] && jk_aligned(h[t]));
         in.p[t] = h[t];
     }
     const size_t n4 = (size_t)n_rows * (d / 4);
@@ -113,10 +101,10 @@ extern "C" int bmp_jk_mean_fwd(const float* const* h, int T, int n_rows, int d, 
 
 // ... and its backward: dh[t] [n_rows x d] = dy / T for every t.
 extern "C" int bmp_jk_mean_bwd(const float* dy, int T, int n_rows, int d, float* const* dh, hipStream_t st) {
-    BMP_REQUIRE(dy && jkt_aligned(dy) && dh && T >= 1 && T <= JK_MAXT && n_rows > 0 && d > 0 && d % 4 == 0);
+    BMP_REQUIRE(dy && jk_aligned(dy) && dh && T >= 1 && T <= JK_MAXT && n_rows > 0 && d > 0 && d % 4 == 0);
     JkOut out = {};
     for (int t = 0; t < T; ++t) {
-        BMP_REQUIRE(dh[t] && jkt_aligned(dh[t]));
+        BMP_REQUIRE(dh[t] && jk_aligned(dh[t]));
         out.p[t] = dh[t];
     }
     const size_t n4 = (size_t)n_rows * (d / 4);

@@ -40,10 +40,8 @@ extern "C" int bmp_ggnn_loop_step_tile_fwd(const float* h, int n_tiles, int d, i
                                            const float* csr_val, const float* WTp, const float* bE, const float* WsTp, const float* bs,
                                            const float* ATp, const float* UcTp, const float* b, float* m, float* rz, float* c,
                                            float* hout, hipStream_t st) {
-    BMP_REQUIRE(h && n_tiles > 0 && bmp_ggnn_loop_step_supported(d) && csr_ptr && WTp && bE && WsTp && bs && ATp && b && hout);
-    BMP_REQUIRE((first || UcTp) && (m == nullptr) == (rz == nullptr) && (m == nullptr) == (c == nullptr));
-    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WTp | (uintptr_t)bE | (uintptr_t)WsTp | (uintptr_t)bs | (uintptr_t)ATp | (uintptr_t)UcTp |
-                  (uintptr_t)m | (uintptr_t)rz | (uintptr_t)c | (uintptr_t)hout) & 15) == 0);
+    BMP_REQUIRE(bE && bs && (((uintptr_t)bE | (uintptr_t)bs) & 15) == 0);
+    if (int rc = wg_fwd_check(bmp_ggnn_loop_step_supported(d), h, n_tiles, first, csr_ptr, WTp, WsTp, ATp, UcTp, b, m, rz, c, hout)) return rc;
     if (first)
         WT_LAUNCH(k_loop_step_first_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, WTp, bE, WsTp, bs, ATp, UcTp, b, m, rz, c, hout);
     else
@@ -57,10 +55,7 @@ extern "C" int bmp_ggnn_loop_step_tile_bwd(const float* dhout, const float* h, c
                                            int first, const int* csrT_ptr, const int* csrT_col, const float* csrT_val,
                                            const float* Wnat_p, const float* Ws_p, const float* A_p, const float* Uc_p, float* dh,
                                            float* gda, float* rh, hipStream_t st) {
-    BMP_REQUIRE(dhout && h && rz && c && n_tiles > 0 && bmp_ggnn_loop_step_supported(d) && csrT_ptr && Wnat_p && Ws_p && A_p && dh && gda);
-    BMP_REQUIRE(first || (Uc_p && rh));
-    BMP_REQUIRE((((uintptr_t)dhout | (uintptr_t)h | (uintptr_t)rz | (uintptr_t)c | (uintptr_t)Wnat_p | (uintptr_t)Ws_p | (uintptr_t)A_p |
-                  (uintptr_t)Uc_p | (uintptr_t)dh | (uintptr_t)gda | (uintptr_t)rh) & 15) == 0);
+    if (int rc = wg_bwd_check(bmp_ggnn_loop_step_supported(d), dhout, h, rz, c, n_tiles, first, csrT_ptr, Wnat_p, Ws_p, A_p, Uc_p, dh, gda, rh)) return rc;
     if (first)
         WT_LAUNCH(k_loop_step_first_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dhout, h, rz, c, csrT_ptr, csrT_col, csrT_val, Wnat_p, Ws_p, A_p, Uc_p, dh, gda, rh);
     else

@@ -30,11 +30,6 @@ template <int D> __global__ __launch_bounds__(512) void k_loop_step_later_table_
 extern "C" int bmp_ggnn_loop_step_supported(int d);           // bmp_loop.hip
 extern "C" int bmp_ggnn_loop_step_table_supported(int d) { return bmp_ggnn_loop_step_supported(d); }
 
-// a tile table is both arrays, and a fixed stride (0: dense rows) is whole 32-row blocks and holds the tallest tile
-static bool loop_table_ok(const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride) {
-    return mt_row0 && mt_nblk && mt_rows > 0 && (tile_stride == 0 || (tile_stride >= WT_R && tile_stride % 32 == 0));
-}
-
 // bmp_ggnn_loop_step_tile_fwd over a tile table: n_tiles table entries, mt_rows rows in the arrays; tile_stride 0 (dense rows) or
 // the fixed stride of the table's tiles, whose dead rows are then cleared in m, rz, c and hout.
 extern "C" int bmp_ggnn_loop_step_table_fwd(const float* h, int n_tiles, int d, int first, const int* csr_ptr, const int* csr_col,
@@ -42,12 +37,9 @@ extern "C" int bmp_ggnn_loop_step_table_fwd(const float* h, int n_tiles, int d, 
                                             const float* ATp, const float* UcTp, const float* b, float* m, float* rz, float* c,
                                             float* hout, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
                                             hipStream_t st) {
-    BMP_REQUIRE(loop_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride));
-    BMP_REQUIRE(h && n_tiles > 0 && bmp_ggnn_loop_step_table_supported(d) && csr_ptr && WTp && bE && WsTp && bs &&
-                ATp && b && hout);
-    BMP_REQUIRE((first || UcTp) && (m == nullptr) == (rz == nullptr) && (m == nullptr) == (c == nullptr));
-    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WTp | (uintptr_t)bE | (uintptr_t)WsTp | (uintptr_t)bs | (uintptr_t)ATp | (uintptr_t)UcTp |
-                  (uintptr_t)m | (uintptr_t)rz | (uintptr_t)c | (uintptr_t)hout) & 15) == 0);
+    BMP_REQUIRE(bmp_tile_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride, WT_R));
+    BMP_REQUIRE(bE && bs && (((uintptr_t)bE | (uintptr_t)bs) & 15) == 0);
+    if (int rc = wg_fwd_check(bmp_ggnn_loop_step_table_supported(d), h, n_tiles, first, csr_ptr, WTp, WsTp, ATp, UcTp, b, m, rz, c, hout)) return rc;
     const WgTable tt = {mt_row0, mt_nblk, mt_rows, tile_stride};
     if (first)
         WT_LAUNCH(k_loop_step_first_table_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, WTp, bE, WsTp, bs, ATp, UcTp, b, m, rz, c, hout, tt);
@@ -62,12 +54,8 @@ extern "C" int bmp_ggnn_loop_step_table_bwd(const float* dhout, const float* h, 
                                             const float* Wnat_p, const float* Ws_p, const float* A_p, const float* Uc_p, float* dh,
                                             float* gda, float* rh, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
                                             hipStream_t st) {
-    BMP_REQUIRE(loop_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride));
-    BMP_REQUIRE(dhout && h && rz && c && n_tiles > 0 && bmp_ggnn_loop_step_table_supported(d) && csrT_ptr &&
-                Wnat_p && Ws_p && A_p && dh && gda);
-    BMP_REQUIRE(first || (Uc_p && rh));
-    BMP_REQUIRE((((uintptr_t)dhout | (uintptr_t)h | (uintptr_t)rz | (uintptr_t)c | (uintptr_t)Wnat_p | (uintptr_t)Ws_p | (uintptr_t)A_p |
-                  (uintptr_t)Uc_p | (uintptr_t)dh | (uintptr_t)gda | (uintptr_t)rh) & 15) == 0);
+    BMP_REQUIRE(bmp_tile_table_ok(mt_row0, mt_nblk, mt_rows, tile_stride, WT_R));
+    if (int rc = wg_bwd_check(bmp_ggnn_loop_step_table_supported(d), dhout, h, rz, c, n_tiles, first, csrT_ptr, Wnat_p, Ws_p, A_p, Uc_p, dh, gda, rh)) return rc;
     const WgTable tt = {mt_row0, mt_nblk, mt_rows, tile_stride};
     if (first)
         WT_LAUNCH(k_loop_step_first_table_bwd, d, n_tiles, wt_lds_bytes(d), st, dhout, h, rz, c, csrT_ptr, csrT_col, csrT_val, Wnat_p, Ws_p, A_p, Uc_p, dh, gda, rh, tt);

@@ -370,3 +370,25 @@ __device__ __forceinline__ void wg_step_bwd(const float* __restrict__ dhout, con
         *(f32x4*)(dh + x) = dv;
     }
 }
+
+// What every self-loop and edge-network entry refuses before its launch, one function per direction: the _tile_ and _table_
+// entries of the self loop (bmp_loop.hip, bmp_loop_table.hip) and the edge network's (bmp_edge.hip) call it.  d_ok: the family's
+// bmp_ggnn_*_step_supported(d); W5: WsT / BT.  The self loop's biases, the edge network's segments and the table are the entries' own.
+static inline int wg_fwd_check(bool d_ok, const float* h, int n_tiles, int first, const int* csr_ptr, const float* WTp, const float* W5p,
+                               const float* ATp, const float* UcTp, const float* b, const float* m, const float* rz, const float* c,
+                               const float* hout) {
+    BMP_REQUIRE(h && n_tiles > 0 && d_ok && csr_ptr && WTp && W5p && ATp && b && hout);
+    BMP_REQUIRE((first || UcTp) && (m == nullptr) == (rz == nullptr) && (m == nullptr) == (c == nullptr));
+    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WTp | (uintptr_t)W5p | (uintptr_t)ATp | (uintptr_t)UcTp | (uintptr_t)m | (uintptr_t)rz |
+                  (uintptr_t)c | (uintptr_t)hout) & 15) == 0);
+    return 0;
+}
+static inline int wg_bwd_check(bool d_ok, const float* dhout, const float* h, const float* rz, const float* c, int n_tiles, int first,
+                               const int* csrT_ptr, const float* Wnat_p, const float* W5_p, const float* A_p, const float* Uc_p,
+                               const float* dh, const float* gda, const float* rh) {
+    BMP_REQUIRE(dhout && h && rz && c && n_tiles > 0 && d_ok && csrT_ptr && Wnat_p && W5_p && A_p && dh && gda);
+    BMP_REQUIRE(first || (Uc_p && rh));
+    BMP_REQUIRE((((uintptr_t)dhout | (uintptr_t)h | (uintptr_t)rz | (uintptr_t)c | (uintptr_t)Wnat_p | (uintptr_t)W5_p | (uintptr_t)A_p |
+                  (uintptr_t)Uc_p | (uintptr_t)dh | (uintptr_t)gda | (uintptr_t)rh) & 15) == 0);
+    return 0;
+}

@@ -215,4 +215,23 @@ static inline int jk_blocks(size_t n4) {
         default: return -1000 - __LINE__;                                                             \
     }
 
+static inline bool jk_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// What every step entry refuses before its launch, one function per direction: the _tile_ entries (bmp_jk.hip) and the _table_
+// entries (bmp_jk_table.hip, behind their table's own check) call it.  d_ok: the entry's bmp_jk_step_*supported(d).
+static inline int jk_fwd_check(bool d_ok, int ng, const float* h, int n_tiles, const int* csr_ptr, const float* WTp, const float* bE,
+                               const float* WsTp, const float* bs, const float* AUp, const float* bU, const float* m, const float* out) {
+    BMP_REQUIRE((ng == 1 || ng == 2) && h && n_tiles > 0 && d_ok);
+    BMP_REQUIRE(csr_ptr && WTp && bE && AUp && bU && out && (WsTp == nullptr) == (bs == nullptr));
+    BMP_REQUIRE(jk_aligned(h) && jk_aligned(WTp) && jk_aligned(bE) && jk_aligned(WsTp) && jk_aligned(bs) && jk_aligned(AUp) &&
+                jk_aligned(m) && jk_aligned(out));
+    return 0;
+}
+static inline int jk_bwd_check(bool d_ok, int ng, const float* dout, const float* out, int n_tiles, const int* csrT_ptr,
+                               const float* Wnat_p, const float* Ws_p, const float* Unat_p, const float* dh, const float* gda) {
+    BMP_REQUIRE((ng == 1 || ng == 2) && dout && out && n_tiles > 0 && d_ok);
+    BMP_REQUIRE(csrT_ptr && Wnat_p && Unat_p && dh && gda);
+    BMP_REQUIRE(jk_aligned(dout) && jk_aligned(out) && jk_aligned(Wnat_p) && jk_aligned(Ws_p) && jk_aligned(Unat_p) && jk_aligned(dh) &&
+                jk_aligned(gda));
+    return 0;
+}

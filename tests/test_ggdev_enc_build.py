@@ -9,11 +9,11 @@ import tempfile
 import numpy as np
 import pytest
 
+from enc_tables import TABLES, _hand_store
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gcn-bmp_amd", "csrc")
 NEW = ("bmp_ggnn_loop_step_table_fwd", "bmp_ggnn_loop_step_table_bwd")
-COUNTS = [31, 32, 33, 63, 64, 95, 96, 127, 2, 5]       # the hand-made store of tests/test_gpu_ggate_enc.py
-TABLES = {"own": (list(range(10)), 256), "shared": (list(range(10)), 2), "seven": ([8, 9, 8, 9, 0, 8, 9], 1)}
 
 
 def _header_args(name):
@@ -59,21 +59,6 @@ def test_table_kernels_do_not_spill():
     assert all(s == 0 for s in scratch), dict(zip(names, scratch))
     assert all(v + a <= 256 for v, a in zip(vgpr, agpr)), dict(zip(names, zip(vgpr, agpr)))
     assert all(o >= 2 for o in occ), dict(zip(names, occ))       # the 8 waves of a workgroup: two per SIMD
-
-
-def _hand_store():
-    """tests/test_gpu_ggate_enc.py's: chains whose bonds cycle through the four types, closed into a ring where there are atoms
-    enough (the plan reads the atom and bond counts only)."""
-    from bmp import synth
-    rs = np.random.RandomState(77)
-    mols = []
-    for n in COUNTS:
-        atoms = synth._ATOM_Z[rs.choice(len(synth._ATOM_Z), size=n, p=synth._ATOM_P)].astype(np.int32)
-        bonds = [(i, i + 1, (i + n) % 4) for i in range(n - 1)]
-        if n > 4:
-            bonds += [(0, n - 1, 3), (1, n - 2, 1)]
-        mols.append(synth.Molecule(atoms, np.asarray(bonds, dtype=np.int32).reshape(-1, 3)))
-    return mols
 
 
 def test_the_three_tables_have_their_properties():

@@ -20,32 +20,15 @@ pytestmark = pytest.mark.gpu
 import ggate_ref as G                                  # noqa: E402
 import ggate32_ref as R                                # noqa: E402
 from oracle import ref_cpu as O                        # noqa: E402
+from enc_tables import COUNTS, TABLES, _hand_store     # noqa: E402,F401 (test_gpu_ggdev_enc.py takes them from here)
 from parity_util import close                          # noqa: E402
 from test_gpu_ops import dev, to_dev                   # noqa: E402
 
 T = torch.from_numpy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 D = 32
-COUNTS = [31, 32, 33, 63, 64, 95, 96, 127, 2, 5]
 KIND = {"fuse": 0, "gate": 1}
 _CACHE = {}
-
-
-def _hand_store():
-    """Chains whose bonds cycle through the four types, closed into a ring where there are atoms enough."""
-    from bmp import synth
-    rs = np.random.RandomState(77)
-    mols = []
-    for n in COUNTS:
-        atoms = synth._ATOM_Z[rs.choice(len(synth._ATOM_Z), size=n, p=synth._ATOM_P)].astype(np.int32)
-        bonds = [(i, i + 1, (i + n) % 4) for i in range(n - 1)]
-        if n > 4:
-            bonds += [(0, n - 1, 3), (1, n - 2, 1)]
-        mols.append(synth.Molecule(atoms, np.asarray(bonds, dtype=np.int32).reshape(-1, 3)))
-    return mols
-
-
-TABLES = {"own": (list(range(10)), 256), "shared": (list(range(10)), 2), "seven": ([8, 9, 8, 9, 0, 8, 9], 1)}
 
 
 def _table(name):
