@@ -72,6 +72,9 @@ SIGNATURES = {
     "bmp_gin_layer_supported": (_I, [_I]),
     "bmp_gin_layer_tile_fwd": (_I, [_P, _I, _I] + [_P] * 12),
     "bmp_gin_layer_tile_bwd": (_I, [_P, _P, _P, _P, _I, _I] + [_P] * 9),
+    "bmp_gin_layer_table_supported": (_I, [_I]),
+    "bmp_gin_layer_table_fwd": (_I, [_P, _I, _I] + [_P] * 13 + [_I, _I, _P]),
+    "bmp_gin_layer_table_bwd": (_I, [_P, _P, _P, _P, _I, _I] + [_P] * 10 + [_I, _I, _P]),
     "bmp_ggnn_gate_step_supported": (_I, [_I]),
     "bmp_ggnn_gate_step_tile_fwd": (_I, [_I, _P, _I, _I] + [_P] * 12),
     "bmp_ggnn_gate_step_tile_bwd": (_I, [_I, _P, _P, _P, _P, _P, _I, _I] + [_P] * 8),

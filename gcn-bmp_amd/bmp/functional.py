@@ -1082,19 +1082,33 @@ class NFPReadoutFn(Function):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Graph isomorphism network layer (models/gin.py:89-128; csrc/bmp_gin.hip).
+# Graph isomorphism network layer (models/gin.py:89-128; csrc/bmp_gin.hip, csrc/bmp_gin_table.hip).  On the tile-table seam
+# below (_table_ok, _table_args, _goes_fused).
 # ---------------------------------------------------------------------------------------------------------
-GIN_PATHS = {"fused": 0, "composed": 0}          # forward calls per form
+GIN_PATHS = {"fused": 0, "composed": 0}          # forward calls per form (a table kernel call counts as fused)
+# On a tile table (the encoder layout, with or without dedup, and the fixed-shape batch): the widths whose table kernels (csrc/
+# bmp_gin_table.hip) beat the composed form, layer forward + backward with weight gradients, by more than the two forms' p90 -
+# median spreads together in at least three of four runs on the 1024-pair DDI-shaped batch in BOTH table layouts (tools/
+# gin_table_probe.py, profiles/gin_table_probe.json); a width set to False here stays composed on table batches,
+# its kernels reachable through GinLayerFn or by setting the entry.  Measured: both widths pass in 4 of 4 runs in both layouts
+# (d = 64: 180 against 411 us without dedup, 154 against 297 us with it; d = 128: 278 against 608 us and 156 against 363 us).
+GIN_TABLE_DEFAULT = {64: True, 128: True}
 
 
 def gin_layer_supported(d: int) -> bool:
     return bool(_lib.lib().bmp_gin_layer_supported(int(d)))
 
 
+def gin_table_ok(pb, d: int) -> bool:
+    """The batch carries a tile table the GIN layer's table kernels take."""
+    return _table_ok(pb) and bool(_lib.lib().bmp_gin_layer_table_supported(int(d)))
+
+
 class GinLayerFn(Function):
     """GINUpdate.__call__ (models/gin.py:89-128) as ONE fused kernel per tile and direction: out = relu(keep * (relu(s . W1T + b1)
     . W2T + b2)), s = h + the type-blind neighbour sum.  W1T / W2T [d x d] K-major (the transposed Linear weights), keep [N x d]
-    (0 or 1 / (1 - p)) or None.  d in {64, 128}, whole tiles (whole_tiles_ok); the other shapes go through ``gin_layer``."""
+    (0 or 1 / (1 - p)) or None.  d in {64, 128}, whole tiles (whole_tiles_ok) or a tile table (gin_table_ok: the grid is the
+    table's pb.n_mtiles entries; with autograd off the table kernel keeps no s / t); the other shapes go through ``gin_layer``."""
 
     @staticmethod
     def forward(ctx, x, W1T, b1, W2T, b2, keep, pb):
@@ -1104,7 +1118,8 @@ class GinLayerFn(Function):
         N, d = x.shape
         if tuple(W1T.shape) != (d, d) or tuple(W2T.shape) != (d, d) or tuple(b1.shape) != (d,) or tuple(b2.shape) != (d,):
             raise ValueError("gin layer: weight shapes do not match x")
-        if not (whole_tiles_ok(pb) and gin_layer_supported(d)):
+        table = gin_table_ok(pb, d)
+        if not (table or (whole_tiles_ok(pb) and gin_layer_supported(d))):
             raise ValueError("gin layer: the fused kernels take d in {64, 128} on whole tiles; use gin_layer()")
         if keep is not None:
             require_rows(keep, "gin layer: keep", d)
@@ -1113,11 +1128,17 @@ class GinLayerFn(Function):
         b1, b2 = b1.contiguous(), b2.contiguous()
         W1p, W2p = pack_k4(W1T), pack_k4(W2T)
         f = lambda: torch.empty(N, d, dtype=torch.float32, device=x.device)
-        s, t, out = f(), f(), f()
-        check(L.bmp_gin_layer_tile_fwd(ptr(x), pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(W1p), ptr(b1),
-                                       ptr(W2p), ptr(b2), ptr(keep), ptr(s), ptr(t), ptr(out), stream()), "bmp_gin_layer_tile_fwd")
-        ctx.save_for_backward(W1T, W2T, s, t, out, keep if keep is not None else torch.empty(0))
-        ctx.pb, ctx.has_keep = pb, keep is not None
+        # forward-only evaluation (under no_grad no input needs a gradient; inside a Function's forward the grad mode itself is
+        # always off): the table kernel stores no s / t
+        infer = table and not any(ctx.needs_input_grad)
+        s, t, out = (None if infer else f()), (None if infer else f()), f()
+        name = f"bmp_gin_layer_{'table' if table else 'tile'}_fwd"
+        check(getattr(L, name)(ptr(x), pb.n_mtiles if table else pb.n_tiles, d, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
+                               ptr(W1p), ptr(b1), ptr(W2p), ptr(b2), ptr(keep), ptr(s), ptr(t), ptr(out), *_table_args(pb, table),
+                               stream()), name)
+        if not infer:
+            ctx.save_for_backward(W1T, W2T, s, t, out, keep if keep is not None else torch.empty(0))
+        ctx.pb, ctx.has_keep, ctx.table = pb, keep is not None, table
         GIN_PATHS["fused"] += 1
         return out
 
@@ -1125,28 +1146,30 @@ class GinLayerFn(Function):
     def backward(ctx, dout):
         L = _lib.lib()
         W1T, W2T, s, t, out, keep = ctx.saved_tensors
-        pb = ctx.pb
+        pb, table = ctx.pb, ctx.table
         keep = keep if ctx.has_keep else None
         dout = dout.contiguous()
         N, d = s.shape
         W2np, W1np = pack_k4(W2T.t()), pack_k4(W1T.t())
         f = lambda: torch.empty(N, d, dtype=torch.float32, device=s.device)
         dp2, dp1, dh = f(), f(), f()
-        check(L.bmp_gin_layer_tile_bwd(ptr(dout), ptr(out), ptr(keep), ptr(t), pb.n_tiles, d, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
-                                       ptr(pb.csrT_val), ptr(W2np), ptr(W1np), ptr(dp2), ptr(dp1), ptr(dh), stream()),
-              "bmp_gin_layer_tile_bwd")
+        name = f"bmp_gin_layer_{'table' if table else 'tile'}_bwd"
+        check(getattr(L, name)(ptr(dout), ptr(out), ptr(keep), ptr(t), pb.n_mtiles if table else pb.n_tiles, d, ptr(pb.csrT_ptr),
+                               ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(W2np), ptr(W1np), ptr(dp2), ptr(dp1), ptr(dh),
+                               *_table_args(pb, table), stream()), name)
         dW2T, db2 = _linear_wgrad(t, dp2)
         dW1T, db1 = _linear_wgrad(s, dp1)
         return dh, dW1T, db1, dW2T, db2, None, None
 
 
 def gin_layer(x, W1T, b1, W2T, b2, keep, pb, fused=True):
-    """One GIN layer.  The fused kernels where the tensors are on the GPU, the width is supported and no molecule spans tiles;
+    """One GIN layer.  The fused kernels where the tensors are on the GPU, the width is supported and no molecule spans tiles; on a
+    batch with a tile table the table kernels for the widths GIN_TABLE_DEFAULT holds True for;
     otherwise the existing operators, for any width that is a multiple of 8: the message operator with W1 for each of the four
     bond types, no per-type bias and the self connection (W1, b1) under relu -- relu((sum_e agg_e + h) . W1T + b1) --, then the
     row linear with relu (with a dropout mask: identity, the mask, relu).  Both are differentiable through autograd."""
     d = x.shape[1]
-    if fused and x.is_cuda and whole_tiles_ok(pb) and gin_layer_supported(d):
+    if _goes_fused(x, pb, fused, gin_layer_supported(d), GIN_TABLE_DEFAULT.get(d, False) and gin_table_ok(pb, d)):
         return GinLayerFn.apply(x, W1T, b1, W2T, b2, keep, pb)
     GIN_PATHS["composed"] += 1
     t = MsgFn.apply(x, W1T.repeat(4, 1), torch.zeros(4, d, dtype=x.dtype, device=x.device), W1T, b1, pb, ACT["relu"])
@@ -1156,7 +1179,8 @@ def gin_layer(x, W1T, b1, W2T, b2, keep, pb, fused=True):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# The tile-table seam of the step families below (gate, self loop / edge network, jumping knowledge).  A batch is
+# The tile-table seam of the GIN layer above and the step families below (gate, self loop / edge network, jumping knowledge;
+# DESIGN.md 3e).  A batch is
 # whole 128-row tiles (whole_tiles_ok) or carries a tile table (_table_ok: the encoder layout, with or without dedup, and the
 # fixed-shape batch; entry i is rows [mt_row0[i], mt_row0[i] + 32 mt_nblk[i]), and molecules never straddle the table's tiles).
 # A family's ``*_step`` asks _goes_fused whether a call takes its fused Function; the Function picks the C entry

@@ -16,6 +16,11 @@ returns ``(mb, n_message_layers * out_dim)``.
 positions of a molecule are ONE row of the packed layout and share one mask, where the reference draws a mask per padded
 position -- same expectation, not the same random process.
 
+Batch forms: per instance and the fixed-shape batch (``PairBatches(layout="static")``) through ``forward``; the encoder layout,
+with or without ``dedup``, through the rows entry ``encode_rows`` / ``readout_rows`` (``rows_reason`` says what it refuses:
+``concat_hidden`` with more than one layer running, and training dropout).  At d = 64 / 128 the layers of a table batch run on the
+tile-table kernels (csrc/bmp_gin_table.hip, ``Fn.GIN_TABLE_DEFAULT``).
+
 Parameter names follow the reference link tree (embed.W, update_layers.{i}.linear_g1.W/b, update_layers.{i}.linear_g2.W/b,
 readout_layers.{k}.i_layer.W/b, readout_layers.{k}.j_layer.W/b).
 """
@@ -26,7 +31,7 @@ import torch
 from torch import nn
 
 from . import functional as Fn
-from .ggnn import EmbedID, Linear, MAX_ATOMIC_NUM, PackedAtoms, _is_float_atoms, as_packed
+from .ggnn import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON, EmbedID, Linear, MAX_ATOMIC_NUM, PackedAtoms, _is_float_atoms, as_packed
 from .packed import PackedMolBatch
 from .relgcn import GGNNReadout
 
@@ -82,12 +87,49 @@ class GIN(nn.Module):
     def plannable(self) -> bool:
         return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
 
-    def forward(self, atom_array, adj=None, is_real_node=None):
+    def _batch(self, atom_array, adj):
+        """The call's batch, behind the refusals every entry shares (float atom features, a CPU batch)."""
         if _is_float_atoms(atom_array):
             raise NotImplementedError("float atom features (embedding bypass, models/gin.py:207-210) are not supported")
         pb = as_packed(atom_array, adj, self.embed.W.device)
         if not pb.atom_id.is_cuda:
             raise RuntimeError("GIN runs on the GPU only: there is no CPU path (move the model and the batch to the device)")
+        return pb
+
+    @property
+    def encoder_layout_reason(self):
+        """Why ``PairBatches(layout="encoder")`` is refused whatever the mode, if it is (bmp.trainer.PairBatches.check_encoder):
+        concat_hidden with more than one layer reads out after every layer.  The trainer's construction -- concat_hidden with tied
+        weights -- runs ONE layer and one readout and is served."""
+        return CONCAT_LAYOUT_REASON if self.concat_hidden and self.n_concat > 1 else None
+
+    def rows_reason(self):
+        """Why ``encode_rows`` refuses this encoder in its present mode; None: it runs.  (encode_rows cannot see ``dedup``, and
+        one mask per distinct molecule is not the reference's process: training dropout takes the per-instance batch form or
+        layout="static".)"""
+        dropout = DROPOUT_LAYOUT_REASON if self.training and self.dropout_ratio > 0.0 else None
+        return self.encoder_layout_reason or dropout
+
+    def encode_rows(self, pb):
+        """The embedding and the layers WITHOUT the readout: (h, h0) on the rows of ``pb`` -- the entry the pair predictor uses
+        for a batch in the encoder layout (bmp/enclayout.py), whose readout runs on the per-instance rows (``readout_rows``).
+        A molecule taller than a tile goes through the composed operators, as in ``forward``; there is no ``is_real_node`` here."""
+        reason = self.rows_reason()
+        if reason:
+            raise NotImplementedError("encode_rows: " + reason)
+        pb = self._batch(pb, None)
+        pb.check_atom_ids(self.embed.W.shape[0])
+        h0 = h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+        for step in range(self.n_message_layers):                                # :215 -- not range(n_layers)
+            h = self.update_layers[0 if self.weight_tying else step](h, pb, None)
+        return h, h0
+
+    def readout_rows(self, h, h0, pb):
+        """The readout of row tensors that live on ``pb``'s rows (the partner of ``encode_rows``)."""
+        return self.readout_layers[0](h, pb, h0, None)
+
+    def forward(self, atom_array, adj=None, is_real_node=None):
+        pb = self._batch(atom_array, adj)
         row_w = None
         if is_real_node is not None:
             # mask (mb, A) -> per-row weight: a virtual row carries the sum of its positions' masks

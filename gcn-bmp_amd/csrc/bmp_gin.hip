@@ -13,8 +13,9 @@
 // h never leaves the CU between the gather and the second product.  The weight gradients dW2 = dp2^T t, dW1 = dp1^T s and the
 // bias gradients are the caller's two calls of bmp_linear_wgrad on the saved s, t and the dp2, dp1 written here.
 // Weights are K4-packed ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
-// The tile load, the MFMA loop, the wave product, the gather and the launch are the shared ones of bmp_wtile.h.
-#include "bmp_wtile.h"
+// The tile load, the MFMA loop, the wave product, the gather and the launch are the shared ones of bmp_wtile.h; the two bodies
+// are gin_layer_fwd / gin_layer_bwd of bmp_wtile_gin.h, which the tile-table kernels of bmp_gin_table.hip instantiate with VAR.
+#include "bmp_wtile_gin.h"
 
 template <int D>
 __global__ __launch_bounds__(512) void k_gin_tile_fwd(const float* __restrict__ h, const int* __restrict__ ptr, const int* __restrict__ col,
@@ -22,56 +23,7 @@ __global__ __launch_bounds__(512) void k_gin_tile_fwd(const float* __restrict__ 
                                                       const float* __restrict__ b1, const float* __restrict__ W2p,
                                                       const float* __restrict__ b2, const float* __restrict__ keep,
                                                       float* __restrict__ s, float* __restrict__ t, float* __restrict__ out) {
-    constexpr int LD = D + 4, NB = D / 64, F = D / 16;
-    extern __shared__ float sm[];
-    float* ta = sm;
-    float* tb = sm + WT_R * LD;
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    wt_load_tile<D>(ta, h, row0, tid);
-    __syncthreads();
-    {
-        const int row = tid >> 2, q = tid & 3;
-        f32x4 acc[F];
-        wt_tile_gather<D, false>(acc, ta, row, q, row0, ptr, col, val);
-        float* d = tb + row * LD + q * (D / 4);
-        float* gq = s + (size_t)(row0 + row) * D + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) { *(f32x4*)(d + 4 * f) = acc[f]; *(f32x4*)(gq + 4 * f) = acc[f]; }
-    }
-    __syncthreads();
-    f32x16 acc[NB];
-    wt_wave_mma<D>(acc, tb, LD, W1p, D, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-        const float bc = b1[c];
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const float v = acc[nb][reg] + bc;
-            ta[wt_row(wv, reg) * LD + c] = v > 0.f ? v : 0.f;
-        }
-    }
-    __syncthreads();
-    wt_wave_mma<D>(acc, ta, LD, W2p, D, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-        const float bc = b2[c];
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) tb[wt_row(wv, reg) * LD + c] = acc[nb][reg] + bc;
-    }
-    __syncthreads();
-    const f32x4 z4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int i = tid; i < WT_R * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        const size_t g = (size_t)(row0 + r) * D + 4 * q4;
-        *(f32x4*)(t + g) = *(const f32x4*)(ta + r * LD + 4 * q4);
-        f32x4 p = *(const f32x4*)(tb + r * LD + 4 * q4);
-        if (keep) p = p * *(const f32x4*)(keep + g);
-        *(f32x4*)(out + g) = __builtin_elementwise_max(p, z4);
-    }
+    gin_layer_fwd<D>(h, ptr, col, val, W1p, b1, W2p, b2, keep, s, t, out);
 }
 
 template <int D>
@@ -81,53 +33,7 @@ __global__ __launch_bounds__(512) void k_gin_tile_bwd(const float* __restrict__ 
                                                       const float* __restrict__ valT, const float* __restrict__ W2np,
                                                       const float* __restrict__ W1np, float* __restrict__ dp2,
                                                       float* __restrict__ dp1, float* __restrict__ dh) {
-    constexpr int LD = D + 4, NB = D / 64, F = D / 16;
-    extern __shared__ float sm[];
-    float* ta = sm;
-    float* tb = sm + WT_R * LD;
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    for (int i = tid; i < WT_R * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        const size_t g = (size_t)(row0 + r) * D + 4 * q4;
-        const f32x4 ov = *(const f32x4*)(out + g);
-        f32x4 v = *(const f32x4*)(dout + g);
-        if (keep) v = v * *(const f32x4*)(keep + g);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) v[x] = ov[x] > 0.f ? v[x] : 0.f;
-        *(f32x4*)(dp2 + g) = v;
-        *(f32x4*)(ta + r * LD + 4 * q4) = v;
-        *(f32x4*)(tb + r * LD + 4 * q4) = *(const f32x4*)(t + g);
-    }
-    __syncthreads();
-    f32x16 acc[NB];
-    wt_wave_mma<D>(acc, ta, LD, W2np, D, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {             // every (row, column) of B belongs to one lane: in place
-            float* p = tb + wt_row(wv, reg) * LD + c;
-            *p = *p > 0.f ? acc[nb][reg] : 0.f;
-        }
-    }
-    __syncthreads();
-    wt_wave_mma<D>(acc, tb, LD, W1np, D, wv);
-    wt_acc_to_tile<D>(ta, acc, wv);
-    __syncthreads();
-    {
-        const int row = tid >> 2, q = tid & 3;
-        const float* pq = tb + row * LD + q * (D / 4);
-        float* g1 = dp1 + (size_t)(row0 + row) * D + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) *(f32x4*)(g1 + 4 * f) = *(const f32x4*)(pq + 4 * f);
-        f32x4 a[F];
-        wt_tile_gather<D, false>(a, ta, row, q, row0, ptrT, colT, valT);
-        float* gq = dh + (size_t)(row0 + row) * D + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) *(f32x4*)(gq + 4 * f) = a[f];
-    }
+    gin_layer_bwd<D>(dout, out, keep, t, ptrT, colT, valT, W2np, W1np, dp2, dp1, dh);
 }
 
 extern "C" int bmp_gin_layer_supported(int d) { return d == 64 || d == 128; }
@@ -136,8 +42,7 @@ extern "C" int bmp_gin_layer_supported(int d) { return d == 64 || d == 128; }
 extern "C" int bmp_gin_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
                                       const float* W1p, const float* b1, const float* W2p, const float* b2, const float* keep,
                                       float* s, float* t, float* out, hipStream_t st) {
-    BMP_REQUIRE(h && n_tiles > 0 && bmp_gin_layer_supported(d) && csr_ptr && W1p && b1 && W2p && b2 && s && t && out);
-    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)W1p | (uintptr_t)W2p | (uintptr_t)keep | (uintptr_t)s | (uintptr_t)t | (uintptr_t)out) & 15) == 0);
+    if (int rc = gin_fwd_check(bmp_gin_layer_supported(d), s && t, h, n_tiles, csr_ptr, W1p, b1, W2p, b2, keep, s, t, out)) return rc;
     WT_LAUNCH(k_gin_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, W1p, b1, W2p, b2, keep, s, t, out);
     return 0;
 }
@@ -145,9 +50,7 @@ extern "C" int bmp_gin_layer_tile_fwd(const float* h, int n_tiles, int d, const 
 extern "C" int bmp_gin_layer_tile_bwd(const float* dout, const float* out, const float* keep, const float* t, int n_tiles, int d,
                                       const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* W2np,
                                       const float* W1np, float* dp2, float* dp1, float* dh, hipStream_t st) {
-    BMP_REQUIRE(dout && out && t && n_tiles > 0 && bmp_gin_layer_supported(d) && csrT_ptr && W2np && W1np && dp2 && dp1 && dh);
-    BMP_REQUIRE((((uintptr_t)dout | (uintptr_t)out | (uintptr_t)keep | (uintptr_t)t | (uintptr_t)W2np | (uintptr_t)W1np | (uintptr_t)dp2 |
-                  (uintptr_t)dp1 | (uintptr_t)dh) & 15) == 0);
+    if (int rc = gin_bwd_check(bmp_gin_layer_supported(d), dout, out, keep, t, n_tiles, csrT_ptr, W2np, W1np, dp2, dp1, dh)) return rc;
     WT_LAUNCH(k_gin_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dout, out, keep, t, csrT_ptr, csrT_col, csrT_val, W2np, W1np, dp2, dp1, dh);
     return 0;
 }

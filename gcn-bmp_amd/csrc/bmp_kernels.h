@@ -147,6 +147,20 @@ extern "C" int bmp_jk_mean_fwd(const float* const* h, int T, int n_rows, int d, 
 extern "C" int bmp_jk_mean_bwd(const float* dy, int T, int n_rows, int d, float* const* dh, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
+// The GIN layer over a tile table (bmp_gin_table.hip): bmp_gin_layer_table_* of include/bmp.h
+// ---------------------------------------------------------------------------------------------
+extern "C" int bmp_gin_layer_supported(int d);
+extern "C" int bmp_gin_layer_table_supported(int d);
+extern "C" int bmp_gin_layer_table_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                                       const float* W1p, const float* b1, const float* W2p, const float* b2, const float* keep,
+                                       float* s, float* t, float* out, const int* mt_row0, const int* mt_nblk, int mt_rows,
+                                       int tile_stride, hipStream_t st);
+extern "C" int bmp_gin_layer_table_bwd(const float* dout, const float* out, const float* keep, const float* t, int n_tiles, int d,
+                                       const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* W2np,
+                                       const float* W1np, float* dp2, float* dp1, float* dh, const int* mt_row0, const int* mt_nblk,
+                                       int mt_rows, int tile_stride, hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
 // Optional per-kernel-class timing with HIP events (bench.py's roofline leg).  Off by default;
 // the only process-global state in the library.  While a class is armed, every launch of that
 // class is bracketed by two events on the launch stream.

@@ -115,11 +115,12 @@ __device__ __forceinline__ void wt_wave_mma(f32x16 (&acc)[D / 64], const float* 
 }
 
 // tile-local gather of one row's quarter (4 threads per row), type-blind: src[row] (SELF: times self) + the sum over the
-// row's entries of val * src[col - row0]
-template <int D, bool SELF>
+// row's entries of val * src[col - row0].  VAR: called for rows < nrows only (the walk reads ptr[row0 + row + 1]); an entry that
+// points at or behind tile row nrows is skipped.
+template <int D, bool SELF, bool VAR = false>
 __device__ __forceinline__ void wt_tile_gather(f32x4 (&acc)[D / 16], const float* src, int row, int q, int row0,
                                                const int* __restrict__ ptr, const int* __restrict__ col, const float* __restrict__ val,
-                                               float self = 1.f) {
+                                               float self = 1.f, int nrows = WT_R) {
     constexpr int LD = D + 4, F = D / 16;
     const float* s0 = src + row * LD + q * (D / 4);
 #pragma unroll
@@ -129,7 +130,7 @@ __device__ __forceinline__ void wt_tile_gather(f32x4 (&acc)[D / 16], const float
     }
     for (int e = ptr[row0 + row]; e < ptr[row0 + row + 1]; ++e) {
         const int j = (col[e] >> 2) - row0;
-        if ((unsigned)j >= (unsigned)WT_R) continue;          // (molecules never straddle a tile on this path: never taken)
+        if ((unsigned)j >= (unsigned)(VAR ? nrows : WT_R)) continue;      // (molecules never straddle a tile on this path: never taken)
         const float v = val[e];
         const float* s = src + j * LD + q * (D / 4);
 #pragma unroll

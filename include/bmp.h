@@ -208,6 +208,24 @@ int bmp_gin_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_pt
 int bmp_gin_layer_tile_bwd(const float* dout, const float* out, const float* keep, const float* t, int n_tiles, int d,
                            const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* W2np, const float* W1np,
                            float* dp2, float* dp1, float* dh, bmp_stream_t stream);
+/* The same layer -- models/gin.py:89-128 -- over a TILE TABLE (csrc/bmp_gin_table.hip), for batches in the encoder layout and the
+ * fixed-shape batch, under the contract of bmp_jk_step_table_*: n_tiles table entries, entry t = rows [mt_row0[t], mt_row0[t] +
+ * 32 mt_nblk[t]) with 1..4 live 32-row blocks, one workgroup each; no molecule straddles an entry; mt_rows = the rows of the
+ * arrays.  No row behind an entry's live rows is read or written, a CSR entry whose source row lies outside the entry's live rows
+ * is skipped, and the waves of a dead block skip their products.  tile_stride: 0 (dense rows) or the table's fixed stride (a
+ * multiple of 32, >= 128): the rows [mt_row0[t] + 32 mt_nblk[t], mt_row0[t] + tile_stride) are then written as ZEROS in every
+ * array the call writes (fwd: s, t, out; bwd: dp2, dp1, dh).  fwd: s and t may be NULL together (forward-only evaluation,
+ * models/gin.py:89-128 under no-backprop): neither is stored.  Everything else is as for the _tile_ entries, and a table of whole
+ * tiles at 128 t gives their results bit for bit.  d with bmp_gin_layer_table_supported (models/gin.py:89-128 at d = 64 or 128). */
+int bmp_gin_layer_table_supported(int d);
+int bmp_gin_layer_table_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                            const float* W1p, const float* b1, const float* W2p, const float* b2, const float* keep, float* s,
+                            float* t, float* out, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
+                            bmp_stream_t stream);
+int bmp_gin_layer_table_bwd(const float* dout, const float* out, const float* keep, const float* t, int n_tiles, int d,
+                            const int* csrT_ptr, const int* csrT_col, const float* csrT_val, const float* W2np, const float* W1np,
+                            float* dp2, float* dp1, float* dh, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
+                            bmp_stream_t stream);
 
 /* ---- GGNN step with a fuse gate or a simple gate in the GRU's place -- models/ggnn_dev_fuse.py:70-131,
  * models/ggnn_dev_gate.py:73-119 (csrc/bmp_gate.hip) ----
