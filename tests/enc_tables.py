@@ -1,5 +1,5 @@
-"""The hand-made molecule store and the three tile tables of the encoder-layout tests (tests/test_gpu_ggate_enc.py and the files
-that take its tables; their properties: tests/test_ggdev_enc_build.py).  No GPU and no GPU helper is imported here.
+"""The hand-made molecule store and the three tile tables of the encoder-layout tests (tests/table_harness.py hands them to
+the GPU tests of the table families; their properties: tests/test_ggdev_enc_build.py).  No GPU and no GPU helper is imported here.
 
 The store has the atom counts 31, 32, 33, 63, 64, 95, 96, 127, 2, 5: with one tile per molecule (n_cu = 256) the pad row falls on
 the last row of a one-block tile, on the first row of a second block and on row 127 of a full tile; with n_cu = 2 tiles are shared

@@ -1,58 +1,32 @@
 """CPU checks of the tile-table form of the d = 32 gate step and of the gated encoders' ``encode_rows`` / ``readout_rows`` pair:
 the two new C entries in the header and the ctypes table, the new translation unit's kernels at the three-workgroups-per-CU
 design point, the dispatch switch, the three refusals of ``encode_rows`` and the layout check of ``PairBatches``."""
-import os
 import re
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gcn-bmp_amd", "csrc")
+from table_build import CSRC, check_table_entries, enc_batch, resource_usage
+
 NEW = ("bmp_ggnn_gate_step_small_table_fwd", "bmp_ggnn_gate_step_small_table_bwd")
 
 
-def _header_args(name):
-    src = open(os.path.join(ROOT, "include", "bmp.h")).read()
-    m = re.search(r"\bint %s\s*\(([^;]*)\);" % name, src)
-    assert m, name
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
 def test_new_entries_in_header_and_ctypes_table():
-    from bmp import _lib, functional as Fn
-    for name in NEW:
-        args = _header_args(name)
-        assert name in _lib.SIGNATURES, name
-        assert len(args) == len(_lib.SIGNATURES[name][1]), (name, len(args), len(_lib.SIGNATURES[name][1]))
-        # the whole-tile list, then the table: mt_row0, mt_nblk, mt_rows, tile_stride in front of the stream
-        whole = _header_args(name.replace("_table", ""))
-        assert args[:len(whole) - 1] == whole[:-1] and args[-1] == whole[-1], name
-        assert [a.split()[-1].lstrip("*") for a in args[len(whole) - 1:-1]] == ["mt_row0", "mt_nblk", "mt_rows", "tile_stride"], name
-        assert _lib.SIGNATURES[name][1][:len(whole) - 1] == _lib.SIGNATURES[name.replace("_table", "")][1][:-1]
+    from bmp import functional as Fn
+    check_table_entries(NEW, whole_of=lambda name: name.replace("_table", ""))
     assert Fn.GATE_TABLE_DEFAULT.keys() == {"fuse", "gate"} and all(type(v) is bool for v in Fn.GATE_TABLE_DEFAULT.values())
     assert Fn.GATE_PATHS.keys() == {"fused", "composed"}
-    assert hasattr(_lib.lib(), NEW[0]) and hasattr(_lib.lib(), NEW[1])
 
 
 def test_table_kernels_fit_three_workgroups_per_cu():
     """The table instances are the six kernels of their own translation unit: no scratch, and the same LDS and occupancy budget
     as the whole-tile instances."""
-    import __graft_entry__ as g
     with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([g._hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC, "-c",
-                            os.path.join(CSRC, "bmp_gate_small_table.hip"), "-o", os.path.join(tmp, "gate_small_table.o"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    grab = lambda pat: [int(x) for x in re.findall(pat, r.stderr)]
-    scratch, lds, occ = grab(r"ScratchSize \[bytes/lane\]: (\d+)"), grab(r"LDS Size \[bytes/block\]: (\d+)"), \
-        grab(r"Occupancy \[waves/SIMD\]: (\d+)")
+        names, scratch, _vgpr, _agpr, occ, lds = resource_usage("bmp_gate_small_table.hip", tmp)
     assert len(names) == len(scratch) == len(lds) == len(occ) == 6, names
     assert all(s == 0 for s in scratch), dict(zip(names, scratch))
-    ecap = int(re.search(r"#define FZ_ECAP (\d+)", open(os.path.join(CSRC, "bmp_tile.h")).read()).group(1))
+    ecap = int(re.search(r"#define FZ_ECAP (\d+)", open(CSRC + "/bmp_tile.h").read()).group(1))
     dyn = (2 * 128 * 36 + 128 * 4 + 132 + 2 * ecap + 4) * 4
     assert all(s + dyn <= 160 * 1024 // 3 for s in lds), (dict(zip(names, lds)), dyn)
     assert all(o >= 3 for o in occ), dict(zip(names, occ))
@@ -63,15 +37,9 @@ def _enc(kind, **kw):
     return (FuseGGNN if kind == "fuse" else GateGGNN)(out_dim=8, hidden_dim=32, n_layers=2, **kw)
 
 
-def _enc_batch():
-    from bmp import enclayout, packed, synth
-    store = synth.make_store(6, seed=2, n_lo=2, n_hi=20, n_mean=8)
-    return enclayout.encode_from_store(packed.MolStore(store), [np.array([0, 1, 2]), np.array([3, 4, 0])], dedup=True)
-
-
 def test_encoders_have_the_rows_pair_and_refuse_with_their_reasons():
     from bmp import ggnn_gate as G
-    eb = _enc_batch()
+    eb = enc_batch()
     for kind in ("fuse", "gate"):
         enc = _enc(kind)
         assert callable(enc.encode_rows) and callable(enc.readout_rows)

@@ -1,59 +1,31 @@
 """CPU checks of the tile-table form of the self-loop GGNN step and of the ``encode_rows`` / ``readout_rows`` pair of the two
 encoders of bmp/ggnn_dev.py: the new C entries in the header and the ctypes table, the new translation unit's kernels without
 scratch, the dispatch switch, the tables of the GPU tests, the refusals of ``encode_rows`` and the layout check of ``PairBatches``."""
-import os
-import re
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
 from enc_tables import TABLES, _hand_store
+from table_build import check_table_entries, enc_batch, lib, resource_usage
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gcn-bmp_amd", "csrc")
 NEW = ("bmp_ggnn_loop_step_table_fwd", "bmp_ggnn_loop_step_table_bwd")
 
 
-def _header_args(name):
-    src = open(os.path.join(ROOT, "include", "bmp.h")).read()
-    m = re.search(r"\bint %s\s*\(([^;]*)\);" % name, src)
-    assert m, name
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
 def test_new_entries_in_header_and_ctypes_table():
-    from bmp import _lib, functional as Fn
-    for name in NEW:
-        args = _header_args(name)
-        assert name in _lib.SIGNATURES, name
-        assert len(args) == len(_lib.SIGNATURES[name][1]), (name, len(args), len(_lib.SIGNATURES[name][1]))
-        # the whole-tile list, then the table: mt_row0, mt_nblk, mt_rows, tile_stride in front of the stream
-        whole = _header_args(name.replace("_table", "_tile"))
-        assert args[:len(whole) - 1] == whole[:-1] and args[-1] == whole[-1], name
-        assert [a.split()[-1].lstrip("*") for a in args[len(whole) - 1:-1]] == ["mt_row0", "mt_nblk", "mt_rows", "tile_stride"], name
-        assert _lib.SIGNATURES[name][1][:len(whole) - 1] == _lib.SIGNATURES[name.replace("_table", "_tile")][1][:-1]
+    from bmp import functional as Fn
+    check_table_entries(NEW)
     assert Fn.LOOP_TABLE_DEFAULT.keys() == {64, 128} and all(type(v) is bool for v in Fn.LOOP_TABLE_DEFAULT.values())
     assert Fn.LOOP_PATHS.keys() == {"fused", "composed"}
-    L = _lib.lib()
-    assert hasattr(L, NEW[0]) and hasattr(L, NEW[1])
+    L = lib().lib()
     assert [bool(L.bmp_ggnn_loop_step_table_supported(d)) for d in (16, 32, 64, 128, 256)] == [False, False, True, True, False]
 
 
 def test_table_kernels_do_not_spill():
     """The table instances are the eight kernels of their own translation unit: 2 directions x first / later x 2 widths, none
     with scratch, each within the 512 registers a SIMD's lane has for the two waves of a 512-thread workgroup."""
-    import __graft_entry__ as g
     with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([g._hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC, "--cuda-device-only",
-                            "-c", os.path.join(CSRC, "bmp_loop_table.hip"), "-o", os.path.join(tmp, "loop_table.o"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    grab = lambda pat: [int(x) for x in re.findall(pat, r.stderr)]
-    scratch, vgpr, agpr, occ = grab(r"ScratchSize \[bytes/lane\]: (\d+)"), grab(r" VGPRs: (\d+)"), grab(r" AGPRs: (\d+)"), \
-        grab(r"Occupancy \[waves/SIMD\]: (\d+)")
+        names, scratch, vgpr, agpr, occ, _lds = resource_usage("bmp_loop_table.hip", tmp, "--cuda-device-only")
     assert len(names) == len(scratch) == len(vgpr) == len(agpr) == len(occ) == 8, names
     assert sum("table_fwd" in n for n in names) == 4 and sum("table_bwd" in n for n in names) == 4, names
     assert all(s == 0 for s in scratch), dict(zip(names, scratch))
@@ -96,15 +68,9 @@ def _enc(kind, **kw):
     return (DevGGNN if kind == "dev" else SelfLoopGGNN)(out_dim=8, hidden_dim=64, n_layers=2, **kw)
 
 
-def _enc_batch():
-    from bmp import enclayout, packed, synth
-    store = synth.make_store(6, seed=2, n_lo=2, n_hi=20, n_mean=8)
-    return enclayout.encode_from_store(packed.MolStore(store), [np.array([0, 1, 2]), np.array([3, 4, 0])], dedup=True)
-
-
 def test_encoders_have_the_rows_pair_and_refuse_with_their_reasons():
     from bmp import ggnn_gate as G
-    eb = _enc_batch()
+    eb = enc_batch()
     for kind in ("dev", "loop"):
         enc = _enc(kind)
         assert callable(enc.encode_rows) and callable(enc.readout_rows)

@@ -2,49 +2,28 @@
 entries in the header, the ctypes table and the library, the widths they serve, their argument checks (which return before any
 launch: no GPU is needed), the new translation unit's kernels without scratch beside the four whole-tile kernels, the dispatch
 switch, the refusals of ``rows_reason`` and the layout check of ``PairBatches``."""
-import os
 import re
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gcn-bmp_amd", "csrc")
+from table_build import BAD_TABLES, CSRC, P, ROOT, bad_id, check_table_entries, enc_batch, header_args, lib, resource_usage
+
 ENTRIES = ("bmp_gin_layer_table_supported", "bmp_gin_layer_table_fwd", "bmp_gin_layer_table_bwd")
 
 
-def _lib():
-    import __graft_entry__ as g
-    g.build()
-    from bmp import _lib
-    return _lib
-
-
-def _header_args(name):
-    src = open(os.path.join(ROOT, "include", "bmp.h")).read()
-    m = re.search(r"\bint %s\s*\(([^;]*)\);" % name, src)
-    assert m, name
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
 def test_header_and_ctypes_table_declare_the_entry_points():
-    _l = _lib()
+    _l = lib()
     from bmp import functional as Fn
-    header = open(os.path.join(ROOT, "include", "bmp.h")).read()
+    header = open(ROOT + "/include/bmp.h").read()
     assert header.count("models/gin.py:89-128") >= 4           # the whole-tile block and each of the three new entries' block
     for name in ENTRIES:
-        args = _header_args(name)
+        args = header_args(name)
         assert name in _l.SIGNATURES, name
         assert len(args) == len(_l.SIGNATURES[name][1]), (name, len(args), len(_l.SIGNATURES[name][1]))   # one ctypes entry per argument
-    for name in ENTRIES[1:]:
-        # the whole-tile list, then the table: mt_row0, mt_nblk, mt_rows, tile_stride in front of the stream
-        args, whole = _header_args(name), _header_args(name.replace("_table", "_tile"))
-        assert args[:len(whole) - 1] == whole[:-1] and args[-1] == whole[-1], name
-        assert [a.split()[-1].lstrip("*") for a in args[len(whole) - 1:-1]] == ["mt_row0", "mt_nblk", "mt_rows", "tile_stride"], name
-        assert _l.SIGNATURES[name][1][:len(whole) - 1] == _l.SIGNATURES[name.replace("_table", "_tile")][1][:-1]
-    kern = open(os.path.join(CSRC, "bmp_kernels.h")).read()
+    check_table_entries(ENTRIES[1:])
+    kern = open(CSRC + "/bmp_kernels.h").read()
     for name in ENTRIES:
         assert re.search(r'extern "C" int %s\s*\(' % name, kern), name
     assert set(Fn.GIN_TABLE_DEFAULT) == {64, 128}
@@ -53,16 +32,12 @@ def test_header_and_ctypes_table_declare_the_entry_points():
 
 
 def test_library_exports_the_entry_points_and_serves_64_and_128():
-    L = _lib().lib()
+    L = lib().lib()
     for name in ENTRIES:
         assert hasattr(L, name), name
     widths = (8, 16, 24, 32, 40, 64, 128, 256)
     assert [d for d in widths if L.bmp_gin_layer_table_supported(d)] == [64, 128]
     assert all(bool(L.bmp_gin_layer_table_supported(d)) == bool(L.bmp_gin_layer_supported(d)) for d in widths)
-
-
-# Non-null, 16-byte aligned addresses nobody reads: every case below fails an argument check, which returns before any launch.
-P = 0x10000
 
 
 def _fwd(L, d=64, r0=P, nb=P, rows=384, stride=0, s=P, t=P, h=P, n_tiles=3):
@@ -73,16 +48,15 @@ def _bwd(L, d=64, r0=P, nb=P, rows=384, stride=0, dp1=P, n_tiles=3, **_):
     return L.bmp_gin_layer_table_bwd(P, P, None, P, n_tiles, d, P, P, P, P, P, P, dp1, P, r0, nb, rows, stride, None)
 
 
-@pytest.mark.parametrize("bad", [dict(r0=None), dict(nb=None), dict(rows=0), dict(stride=96), dict(stride=130), dict(d=32),
-                                 dict(n_tiles=0)], ids=lambda b: "-".join(f"{k}={v}" for k, v in b.items()))
+@pytest.mark.parametrize("bad", BAD_TABLES + [dict(d=32), dict(n_tiles=0)], ids=bad_id)
 def test_entries_check_their_arguments_before_any_launch(bad):
-    L = _lib().lib()
+    L = lib().lib()
     assert _fwd(L, **bad) < -1000
     assert _bwd(L, **bad) < -1000
 
 
 def test_forward_takes_s_and_t_both_or_neither_and_aligned():
-    L = _lib().lib()
+    L = lib().lib()
     assert _fwd(L, s=None) < -1000 and _fwd(L, t=None) < -1000          # a lone null
     assert _fwd(L, s=P + 4) < -1000 and _fwd(L, h=P + 8) < -1000        # 16-byte alignment, as the whole-tile entry
     assert _bwd(L, dp1=None) < -1000 and _bwd(L, dp1=P + 4) < -1000
@@ -90,24 +64,13 @@ def test_forward_takes_s_and_t_both_or_neither_and_aligned():
     assert L.bmp_gin_layer_tile_fwd(P, 3, 64, P, P, P, P, P, P, P, None, None, None, P, None) < -1000
 
 
-def _resource_usage(src, tmp):
-    import __graft_entry__ as g
-    r = subprocess.run([g._hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC, "--cuda-device-only",
-                        "-c", os.path.join(CSRC, src), "-o", os.path.join(tmp, src + ".o"),
-                        "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    grab = lambda pat: [int(x) for x in re.findall(pat, r.stderr)]
-    return (re.findall(r"Function Name: (\S+)", r.stderr), grab(r"ScratchSize \[bytes/lane\]: (\d+)"), grab(r" VGPRs: (\d+)"),
-            grab(r" AGPRs: (\d+)"), grab(r"Occupancy \[waves/SIMD\]: (\d+)"))
-
-
 def test_table_kernels_do_not_spill_and_the_whole_tile_unit_keeps_its_four():
     """The table instances are the four kernels of their own translation unit -- 2 directions x 2 widths --, none with scratch,
     each within the 512 registers a SIMD's lane has for the two waves of a 512-thread workgroup; bmp_gin.hip still yields its
     four whole-tile kernels and no table instance."""
     with tempfile.TemporaryDirectory() as tmp:
-        names, scratch, vgpr, agpr, occ = _resource_usage("bmp_gin_table.hip", tmp)
-        whole = _resource_usage("bmp_gin.hip", tmp)
+        names, scratch, vgpr, agpr, occ, _lds = resource_usage("bmp_gin_table.hip", tmp, "--cuda-device-only")
+        whole = resource_usage("bmp_gin.hip", tmp, "--cuda-device-only")
     assert len(names) == len(scratch) == len(vgpr) == len(agpr) == len(occ) == 4, names
     assert sum("k_gin_table_fwd" in n for n in names) == 2 and sum("k_gin_table_bwd" in n for n in names) == 2, names
     assert all(s == 0 for s in scratch), dict(zip(names, scratch))
@@ -142,15 +105,9 @@ def test_gin_has_the_rows_entry_and_its_reasons():
     assert plain.train().rows_reason() is None and plain.eval().rows_reason() is None
 
 
-def _enc_batch():
-    from bmp import enclayout, packed, synth
-    store = synth.make_store(6, seed=2, n_lo=2, n_hi=20, n_mean=8)
-    return enclayout.encode_from_store(packed.MolStore(store), [np.array([0, 1, 2]), np.array([3, 4, 0])], dedup=True)
-
-
 def test_encode_rows_refuses_with_the_reasons_before_it_touches_the_batch():
     from bmp.ggnn import CONCAT_LAYOUT_REASON, DROPOUT_LAYOUT_REASON
-    eb = _enc_batch()
+    eb = enc_batch()
     with pytest.raises(NotImplementedError) as e:
         _gin(n_layers=3, concat_hidden=True, weight_tying=False).eval().encode_rows(eb.pb_enc)
     assert str(e.value) == "encode_rows: " + CONCAT_LAYOUT_REASON and "concat_hidden" in str(e.value)

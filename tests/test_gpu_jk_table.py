@@ -2,9 +2,9 @@
 bmp/ggnn_jk.py in the encoder layout, under de-duplication and on the fixed-shape batch.
 
 Tolerances, all the project's: 1e-4 of the tensor's max-abs against the float64 restatement (tests/jk_ref.py), 1e-5 between two
-float32 forms of the same step, 1e-4 for parameters after several replayed steps (test_gpu_static_batch.py).  The store and the
-three tables are tests/test_gpu_ggate_enc.py's (their properties: tests/test_ggdev_enc_build.py), the pairs, the stride case and
-the batch helpers tests/test_gpu_ggdev_enc.py's; every case is under 800 rows at d = 64, one repeats at d = 128.  The tests that
+float32 forms of the same step, 1e-4 for parameters after several replayed steps (test_gpu_static_batch.py).  The store, the
+three tables, the pairs, the stride case and the shared bodies are tests/table_harness.py's (the tables' properties:
+tests/test_ggdev_enc_build.py); every case is under 800 rows at d = 64, one repeats at d = 128.  The tests that
 go through ``jk_step`` force ``JK_TABLE_DEFAULT`` on: they do not depend on the measured default."""
 import ctypes
 
@@ -18,29 +18,24 @@ import jk_ref as R                                     # noqa: E402
 from oracle import ref_cpu as O                        # noqa: E402
 from parity_util import close                          # noqa: E402
 from test_gpu_ops import dev, to_dev                   # noqa: E402
-from test_gpu_ggate_enc import _dense_adj, _static_world, _table                          # noqa: E402
-from test_gpu_ggdev_enc import I1, I2, LAYERS, _atoms_by_molecule, _batches, _pair_run, _stride_case      # noqa: E402
+import table_harness as H                              # noqa: E402
 
 NAMES = ("h", "WT", "bE", "WsT", "bs", "AU", "bU")
-GRADS = ("dh", "dWT", "dbE", "dWsT", "dbs", "dAU", "dbU")
+LABELS = ("out", "dh", "dWT", "dbE", "dWsT", "dbs", "dAU", "dbU")
 KINDS = ((1, False), (2, True), (2, False))            # (ng, self loop): jknet, jk_gru with and without its self loop
+LAYERS = 3
 _CACHE = {}
+
+
+def _paths():
+    from bmp import functional as Fn
+    return Fn.JK_PATHS
 
 
 @pytest.fixture
 def table_on(monkeypatch):
     from bmp import functional as Fn
-    for key in Fn.JK_TABLE_DEFAULT:
-        monkeypatch.setitem(Fn.JK_TABLE_DEFAULT, key, True)
-        monkeypatch.setitem(Fn.JK_STEP_DEFAULT, key, True)
-    return Fn
-
-
-def _took(fn):
-    from bmp import functional as Fn
-    before = dict(Fn.JK_PATHS)
-    out = fn()
-    return out, {k: Fn.JK_PATHS[k] - before[k] for k in before}
+    return H.force_on(monkeypatch, Fn.JK_TABLE_DEFAULT, Fn.JK_STEP_DEFAULT)
 
 
 # ---- one step on the three tables ----
@@ -69,7 +64,7 @@ def _operands(name, d, ng, loop, seed=None):
     """Float64 operands of one step on table ``name`` in the kernel's layouts, drawn once, and the cotangent."""
     key = ("ops", name, d, ng, loop, seed)
     if key not in _CACHE:
-        N = _table(name).pb_enc.n_rows
+        N = H.table(name).pb_enc.n_rows
         g = torch.Generator().manual_seed(SEEDS[(name, d, ng, loop)] if seed is None else seed)
         r = lambda *s: torch.randn(*s, dtype=torch.float64, generator=g)
         nu = ng * d
@@ -125,7 +120,7 @@ def _ref_step(o, adj, d, ng, loop, dtype, backward=True):
 def _kink(name, d, ng, loop, seed=None):
     """(min |pre64|, max |pre32 - pre64|) of the case's float64 and float32 restatements."""
     o = _operands(name, d, ng, loop, seed)
-    adj = _dense_adj(_table(name).pb_enc)
+    adj = H.dense_adj(H.table(name).pb_enc)
     a64 = _ref_step(o, adj, d, ng, loop, torch.float64, backward=False)[1]
     a32 = _ref_step(o, adj, d, ng, loop, torch.float32, backward=False)[1]
     return a64.abs().min().item(), (a32.double() - a64).abs().max().item()
@@ -146,7 +141,7 @@ def _search_seeds(start=400):
 def _restatement(name, d, ng, loop):
     key = ("ref", name, d, ng, loop)
     if key not in _CACHE:
-        out, _pre, grads = _ref_step(_operands(name, d, ng, loop), _dense_adj(_table(name).pb_enc), d, ng, loop, torch.float64)
+        out, _pre, grads = _ref_step(_operands(name, d, ng, loop), H.dense_adj(H.table(name).pb_enc), d, ng, loop, torch.float64)
         _CACHE[key] = (out, grads)
     return _CACHE[key]
 
@@ -169,44 +164,20 @@ def _run_step(name, d, ng, loop, pb, fused):
     return out.detach(), {k: (None if q[k] is None else q[k].grad) for k in NAMES}
 
 
-def _compare(a, b, tag, tol):
-    close(a[0], b[0], f"{tag}: out", tol=tol)
-    for k, nm in zip(NAMES, GRADS):
-        if b[1][k] is not None:
-            close(a[1][k], b[1][k], f"{tag}: {nm}", tol=tol)
-
-
 @pytest.mark.parametrize("ng,loop", KINDS)
 @pytest.mark.parametrize("name,d", [("own", 64), ("shared", 64), ("seven", 64), ("own", 128)])
 def test_table_step_against_composed_and_restatement(name, d, ng, loop, table_on):
     Fn = table_on
-    pb = to_dev(_table(name).pb_enc)
-    r0, nb = pb.mt_row0.cpu().numpy(), pb.mt_nblk.cpu().numpy()
-    cover = np.zeros(pb.n_rows, dtype=int)
-    for a, k in zip(r0, nb):
-        cover[a:a + 32 * k] += 1
-    assert (cover == 1).all() and pb.n_rows < 800        # the table's tiles abut and hold every row once
+    pb = H.table_on_device(name)
     lo, err = _kink(name, d, ng, loop)
     print(f"[kink] {name} d={d} ng={ng} loop={loop}: min |pre64| {lo:.3e}, max |pre32 - pre64| {err:.3e}, margin {lo / err:.1f} x")
     assert lo >= R.KINK_FACTOR * err, (lo, err)          # no relu of the case sits on its kink at float32 precision
-    ref = _restatement(name, d, ng, loop)
-    fused, took = _took(lambda: _run_step(name, d, ng, loop, pb, True))
-    assert took == {"fused": 1, "composed": 0}, took
-    comp, took = _took(lambda: _run_step(name, d, ng, loop, pb, False))
-    assert took == {"fused": 0, "composed": 1}, took
-    tag = f"{name} d={d} ng={ng} loop={loop}"
-    _compare(fused, comp, f"table {tag} vs composed", 1e-5)
-    _compare(fused, ref, f"table {tag} vs float64", 1e-4)
-    _compare(comp, ref, f"composed {tag} vs float64", 1e-4)
-    again = _run_step(name, d, ng, loop, pb, True)
-    assert torch.equal(again[0], fused[0])
-    assert all(torch.equal(again[1][k], fused[1][k]) for k in NAMES if fused[1][k] is not None)
-    with torch.no_grad():                                # forward-only evaluation: null m
-        args = list(_args(_operands(name, d, ng, loop), False).values())
-        o0, took = _took(lambda: Fn.JKStepFn.apply(*args, pb))
-        assert took == {"fused": 1, "composed": 0} and torch.equal(o0, fused[0])
-        o1, took = _took(lambda: Fn.jk_step(*args, pb))                   # ... and what jk_step picks with the switch on
-        assert took == {"fused": 1, "composed": 0} and torch.equal(o1, fused[0])
+    args = list(_args(_operands(name, d, ng, loop), False).values())
+    H.step_against_composed_and_restatement(
+        _paths(), lambda fused: _run_step(name, d, ng, loop, pb, fused), _restatement(name, d, ng, loop),
+        f"{name} d={d} ng={ng} loop={loop}", NAMES, LABELS,
+        [lambda: Fn.JKStepFn.apply(*args, pb),           # forward-only evaluation: null m
+         lambda: Fn.jk_step(*args, pb)])                 # ... and what jk_step picks with the switch on
 
 
 # ---- through the C ABI ----
@@ -243,29 +214,22 @@ def _abi_bwd(entry, ng, d, n_tiles, dout, out, csrT, W, dh, gda, tab=()):
 def test_table_of_whole_tiles_is_the_whole_tile_kernel_bit_for_bit(d, ng, loop):
     """Every table entry a four-block tile at 128 t, on the whole-tile batch of tests/jk_ref.py's "fixture" (three tiles, all four
     bond types): the products run in the same order, so every written array is bit-identical."""
-    from bmp._lib import ptr
     pb = to_dev(R.data("fixture")["pb"])
-    assert pb.mt_row0 is None and not pb.oversized and pb.n_tiles >= 3
     N, nt = pb.n_rows, pb.n_tiles
     csr, csrT = (pb.csr_ptr, pb.csr_col, pb.csr_val), (pb.csrT_ptr, pb.csrT_col, pb.csrT_val)
     W = _weights(d, ng, loop, 40 + d)
     g = torch.Generator().manual_seed(41)
     h, dout = torch.randn(N, d, generator=g).to(dev()), torch.randn(N, ng * d, generator=g).to(dev())
-    r0 = torch.arange(nt, dtype=torch.int32, device=dev()) * 128
-    nb = torch.full((nt,), 4, dtype=torch.int32, device=dev())
-    res = {}
-    for entry, tab in (("tile", ()), ("table", (ptr(r0), ptr(nb), N, 0))):
+
+    def run(entry, tab):
         z = lambda n: torch.zeros(N, n, device=dev())
         m, out, dh, gda = z(d), z(ng * d), z(d), z((5 if loop else 4) * d + ng * d)
         _abi_fwd(entry, ng, d, nt, h, csr, W, m, out, tab)
         _abi_bwd(entry, ng, d, nt, dout, out, csrT, W, dh, gda, tab)
         torch.cuda.synchronize()
-        res[entry] = dict(m=m, out=out, dh=dh, gda=gda)
-    for k, x in res["table"].items():
-        assert torch.isfinite(x).all(), k
-        print(f"[whole tiles] d={d} ng={ng} loop={loop} {k}: max |table - tile| = {(x - res['tile'][k]).abs().max().item():.3e}")
-        assert torch.equal(x, res["tile"][k]), (k, (x - res["tile"][k]).abs().max().item())
-    assert res["table"]["out"].abs().max() > 0 and res["table"]["gda"].abs().max() > 0
+        return dict(m=m, out=out, dh=dh, gda=gda)
+
+    H.whole_tiles_bit_for_bit(pb, run, f"d={d} ng={ng} loop={loop}", ("out", "gda"))
 
 
 @pytest.mark.parametrize("ng,loop", KINDS)
@@ -276,42 +240,27 @@ def test_fixed_stride_clears_the_dead_rows(ng, loop):
     the live rows equal the dense-row run (tile_stride = 0, which leaves the dead rows alone) of the same molecules; the canary
     stays NaN either way."""
     from bmp._lib import ptr
-    d, N, C = 64, 384, 128
-    csr, csrT, r0, nb, live = _stride_case()
+    d, N = 64, H.STRIDE_ROWS
+    csr, csrT, r0, nb, live = H.stride_case((20, 70, 120))
     W = _weights(d, ng, loop, 77)
     g = torch.Generator().manual_seed(9)
     rnd = lambda *s: torch.randn(*s, generator=g).to(dev())
-    nan_dead = lambda x: torch.where(live[:, None], x, torch.full_like(x, float("nan")))
-    h, dout = nan_dead(rnd(N, d)), nan_dead(rnd(N, ng * d))
+    h, dout = H.nan_dead(rnd(N, d), live), H.nan_dead(rnd(N, ng * d), live)
     res = {}
     for stride in (128, 0):
-        nan = lambda n: torch.full((N + C, n), float("nan"), device=dev())
-        m, out, dh, gda = nan(d), nan(ng * d), nan(d), nan((5 if loop else 4) * d + ng * d)
+        m, out, dh, gda = (H.nan_rows(n) for n in (d, ng * d, d, (5 if loop else 4) * d + ng * d))
         tab = (ptr(r0), ptr(nb), N, stride)
         _abi_fwd("table", ng, d, 3, h, csr, W, m, out, tab)
         torch.cuda.synchronize()
         res[stride] = dict(m=m.clone(), out=out.clone())
-        out[:N] = nan_dead(out[:N])                      # the backward's input: dead rows NaN again
+        out[:N] = H.nan_dead(out[:N], live)              # the backward's input: dead rows NaN again
         _abi_bwd("table", ng, d, 3, dout, out, csrT, W, dh, gda, tab)
         torch.cuda.synchronize()
         res[stride].update(dh=dh, gda=gda)
-    for name, x in res[128].items():
-        y = res[0][name]
-        assert torch.isnan(x[N:]).all() and torch.isnan(y[N:]).all(), name       # the canary behind mt_rows
-        x, y = x[:N], y[:N]
-        assert not torch.isnan(x).any(), name
-        assert (x[~live] == 0).all(), name
-        assert torch.isfinite(x[live]).all(), name
-        close(x[live], y[live], f"fixed stride ng={ng} loop={loop}: live rows of {name} vs dense rows", tol=1e-5)
-        assert torch.isnan(y[~live]).all(), name          # (without a stride nothing is written there)
-    assert res[128]["out"][:N][live].abs().max() > 0 and res[128]["gda"][:N][live].abs().max() > 0
-    # the table entries refuse a stride that is no multiple of 32 or shorter than a full tile, and a missing table
+    H.fixed_stride_clears_the_dead_rows(res, live, ("out", "gda"), label=f"ng={ng} loop={loop}")
     out = torch.empty(N, ng * d, device=dev())
-    for tab in ((ptr(r0), ptr(nb), N, 96), (ptr(r0), ptr(nb), N, 130), (None, ptr(nb), N, 0), (ptr(r0), None, N, 0), (ptr(r0), ptr(nb), 0, 0)):
-        with pytest.raises(ValueError, match="argument check failed"):
-            _abi_fwd("table", ng, d, 3, h, csr, W, None, out, tab)
-        with pytest.raises(ValueError, match="argument check failed"):
-            _abi_bwd("table", ng, d, 3, dout, out, csrT, W, dh, gda, tab)
+    H.refuses_the_bad_tables(r0, nb, lambda tab: _abi_fwd("table", ng, d, 3, h, csr, W, None, out, tab),
+                             lambda tab: _abi_bwd("table", ng, d, 3, dout, out, csrT, W, dh, gda, tab))
 
 
 # ---- 'mean' on a row count ----
@@ -375,51 +324,23 @@ def _pair_model(kind, attn, d=64):
 @pytest.mark.parametrize("attn", [None, "nie"])
 @pytest.mark.parametrize("kind", list(KIND))
 def test_encoders_train_in_the_encoder_layout(kind, attn, dedup, n_cu, table_on):
-    pb, t, eb, t2 = _batches(dedup, n_cu)
     model = _pair_model(kind, attn)
     assert model.training and model.graph_conv.rows_reason() is None
-    inst, took = _took(lambda: _pair_run(model, pb, t))
-    assert took == {"fused": LAYERS, "composed": 0}, took
-    at_inst = model.graph_conv.get_atom_array()
-    enc, took = _took(lambda: _pair_run(model, eb, t2))
-    assert took == {"fused": LAYERS, "composed": 0}, took
-    tag = f"{kind} attn={attn} dedup={dedup} n_cu={n_cu}"
-    for k in ("y", "g1", "g2"):
-        close(enc[k], inst[k], f"{tag}: {k} vs per-instance", tol=1e-5)
-    loss_i, loss_e = model.loss(inst["y"], t).detach().reshape(1), model.loss(enc["y"], t2).detach().reshape(1)
-    close(loss_e, loss_i, f"{tag}: loss vs per-instance", tol=1e-5)
-    gmax = max(v.abs().max().item() for v in inst["grads"].values())
-    assert sorted(enc["grads"]) == sorted(inst["grads"])
-    for name, gr in enc["grads"].items():
-        # (1e-3 of the largest gradient as the floor of a parameter's scale: test_gpu_ggate_enc.py)
-        close(gr, inst["grads"][name], f"{tag}: grad {name} vs per-instance", tol=1e-5, floor=1e-3 * gmax)
-    assert any(v.abs().max() > 0 for k, v in enc["grads"].items() if k.startswith("graph_conv/message_layers"))
     # the atom array handed to the co-attention: what the readout read (jknet: the aggregate) on the instance rows
-    at_enc = model.graph_conv.get_atom_array()
-    assert at_enc.pb is eb.pb
-    close(_atoms_by_molecule(at_enc.rows, eb.pb), _atoms_by_molecule(at_inst.rows, pb), f"{tag}: atoms", tol=1e-5)
+    H.encoder_layout_against_per_instance(H.world("hand"), model, _paths(), f"{kind} attn={attn} dedup={dedup} n_cu={n_cu}", dedup, n_cu,
+                                          H.fused(LAYERS), atoms=model.graph_conv.get_atom_array)
 
 
 def test_paths_follow_the_switch(monkeypatch):
     from bmp import functional as Fn
-    pb, t, eb, t2 = _batches(True, 5)
-    model = _pair_model("jk-gru", None)
-    res = {}
-    for on in (True, False):
-        monkeypatch.setitem(Fn.JK_TABLE_DEFAULT, ("jk_gru", 64), on)
-        res[on], took = _took(lambda: _pair_run(model, eb, t2))
-        assert took == ({"fused": LAYERS, "composed": 0} if on else {"fused": 0, "composed": LAYERS}), (on, took)
-    for k in ("y", "g1", "g2"):
-        close(res[True][k], res[False][k], f"table kernels vs composed: {k}", tol=1e-5)
-    gmax = max(v.abs().max().item() for v in res[False]["grads"].values())
-    for name, gr in res[True]["grads"].items():
-        close(gr, res[False]["grads"][name], f"table kernels vs composed: grad {name}", tol=1e-5, floor=1e-3 * gmax)
+    H.paths_follow_the_switch(monkeypatch, H.world("hand"), _pair_model("jk-gru", None), _paths(), Fn.JK_TABLE_DEFAULT, ("jk_gru", 64),
+                              LAYERS)
 
 
 def test_encode_rows_refuses_concat_hidden_training_dropout_and_attn():
     from bmp import ggnn_gate
     from bmp.ggnn_jk import JK_ATTN_LAYOUT_REASON, JKGruGGNN, JKNetGGNN
-    pb, t, eb, t2 = _batches(True, 5)
+    pb, t, eb, t2 = H.batches(H.world("hand"), True, 5)
     for make in (lambda **kw: JKNetGGNN(out_dim=16, hidden_dim=64, n_layers=2, layer_aggr="mean", **kw),
                  lambda **kw: JKGruGGNN(out_dim=16, hidden_dim=64, n_layers=2, self_loop=True, **kw)):
         enc = make(dropout_rate=0.25).to(dev())
@@ -455,95 +376,14 @@ def _static_model(kind="jk-gru+self_loop"):
 
 @pytest.mark.parametrize("kind", ["jk-gru+self_loop", "jknet-mean"])
 def test_static_batch_eager_step_equals_the_packed_step(kind, table_on):
-    """Batch k0 holds the store's tallest molecules and batch k1, loaded into the same arrays afterwards, its shortest: rows that
-    k0 left behind in a dead block would enter k1's weight gradients."""
-    from bmp import packed
-    from bmp.dp import FlatAdam
-    ds, by_size, sizes = _static_world()
-    B = 8
-    model = _static_model(kind)
-    opt = FlatAdam(model, alpha=1e-3)
-    sb = packed.StaticPairBatch(ds, B)
-    rs = np.random.RandomState(4)
-    tall, short = by_size[:2 * B], by_size[-2 * B:]
-    assert min(sizes[k] for k in tall) > 64 and max(sizes[k] for k in short) < 31        # 3-4 live blocks, then one
-    for tag, sel in (("k0 tallest", tall), ("k1 shortest", short)):
-        i1, i2 = sel[:B], sel[B:]
-        lab = rs.randint(0, 2, (B, 1)).astype(np.int32)
-        pb, t = packed.pack_from_store_device(ds, [i1, i2], labels=lab)
-        sb.load([i1, i2], lab); sb.reset_derived(); sb.emit()
-        assert sb.pb.mt_row0 is not None and sb.pb.tile_stride == 128
-        (loss, took) = _took(lambda: opt.functional_loss(pb, t=t))
-        assert took == {"fused": 3, "composed": 0}, took
-        loss.backward(); opt.collect_grads()
-        y_ref, g_ref, l_ref = model.y.detach().clone(), opt.grad.clone(), loss.detach().clone()
-        (loss, took) = _took(lambda: opt.functional_loss(sb.pb, t=sb.t))
-        assert took == {"fused": 3, "composed": 0}, took
-        loss.backward(); opt.collect_grads()
-        close(model.y.detach(), y_ref, f"static {kind} {tag}: logits", tol=1e-5)
-        close(loss.detach().reshape(1), l_ref.reshape(1), f"static {kind} {tag}: loss", tol=1e-5)
-        close(opt.grad, g_ref, f"static {kind} {tag}: flat gradient", tol=1e-5)
+    H.static_eager_step_equals_the_packed_step(_static_model(kind), _paths(), 3, kind)
 
 
 def test_fit_runs_a_jk_gru_model_in_every_layout(table_on):
-    """``fit`` over PairBatches per instance, in the encoder layout with dedup and as replays of one recorded step
-    (layout="static"; the short last batch of a pass runs launch by launch): the same parameters after two passes."""
-    from bmp import packed, synth, trainer as Tr
-    from bmp.dp import FlatAdam
     from bmp.predictor import build_pair_predictor
-    store = synth.make_store(40, seed=3, n_lo=4, n_hi=40, n_mean=16)
-    ds = packed.DeviceMolStore(packed.MolStore(store), dev())
-    rs = np.random.RandomState(1)
-    i1, i2 = rs.randint(0, 40, 200), rs.randint(0, 40, 200)
-    nat = np.array([m.n for m in store])
-    lab = ((nat[i1] + nat[i2]) % 2).astype(np.int32).reshape(-1, 1)
-    runs, took, flat = {}, {}, {}
-    for name, kw in (("instance", {}), ("dedup", dict(layout="encoder", dedup=True)), ("static", dict(layout="static"))):
-        torch.manual_seed(0)
-        model = build_pair_predictor(encoder="ggnn-jk-gru", hidden_dim=64, out_dim=32, n_layers=2, attn="nie", head=4).to(dev())
-        opt = FlatAdam(model, alpha=2e-3)
-        tr = Tr.PairBatches(ds, i1[:144], i2[:144], lab[:144], 32, shuffle=True, seed=2, **kw)
-        va = Tr.PairBatches(ds, i1[144:], i2[144:], lab[144:], 32, **kw)
-        assert len(tr) == 5 and len(va) == 2
-        tr.check_encoder(model)
-        runs[name], took[name] = _took(lambda: Tr.fit(model, opt, tr, va, epochs=2))
-        flat[name] = opt.flat.detach().clone()
-    assert took["dedup"]["composed"] == 0 and took["dedup"]["fused"] > 0, took          # the table kernels, every step
-    assert took["static"]["composed"] == 0 and 0 < took["static"]["fused"] < took["instance"]["fused"], took       # replays
-    for name in ("dedup", "static"):
-        for a, b in zip(runs["instance"], runs[name]):
-            for key in ("main/loss", "validation/main/loss"):
-                print(f"[fit] {name} {key}: {b[key]:.7f} vs per-instance {a[key]:.7f}")
-        close(flat[name], flat["instance"], f"fit jk_gru {name}: parameters after two passes vs per-instance", tol=1e-4)
+    H.fit_runs_in_every_layout(_paths(), lambda: build_pair_predictor(encoder="ggnn-jk-gru", hidden_dim=64, out_dim=32, n_layers=2,
+                                                                     attn="nie", head=4), "jk_gru")
 
 
 def test_static_batch_recorded_step_replays_on_the_table_kernels(table_on):
-    Fn = table_on
-    from bmp import packed
-    from bmp.dp import FlatAdam, GraphedTrainStep
-    ds, by_size, _sizes = _static_world()
-    B, steps = 8, 4
-    eager, graphed = _static_model(), _static_model()
-    oe, og = FlatAdam(eager, alpha=1e-3), FlatAdam(graphed, alpha=1e-3)
-    assert torch.equal(oe.flat, og.flat)
-    sb = packed.StaticPairBatch(ds, B)
-    stepper = GraphedTrainStep(graphed, og)
-    rs = np.random.RandomState(6)
-    order = np.concatenate((by_size[:2 * B], by_size[-2 * B:], rs.permutation(48)[:4 * B]))       # tall, short, then mixed
-    le, lg = [], []
-    for k in range(steps):
-        sel = order[2 * B * k:2 * B * (k + 1)]
-        i1, i2 = sel[:B], sel[B:]
-        lab = rs.randint(0, 2, (B, 1)).astype(np.int32)
-        pb, t = packed.pack_from_store_device(ds, [i1, i2], labels=lab)
-        loss = oe.functional_loss(pb, t=t); loss.backward(); oe.collect_grads(); oe.step()
-        le.append(float(loss.detach()))
-        sb.load([i1, i2], lab)
-        mark = dict(Fn.JK_PATHS)
-        lg.append(float(stepper(sb).detach()))
-        assert Fn.JK_PATHS["composed"] == mark["composed"]            # the recording took the table kernels, every call of it
-        assert (Fn.JK_PATHS["fused"] > mark["fused"]) == (k == 0)     # ... and a replay runs no Python step
-    assert len(stepper.graphs) == 1 and og.t == oe.t == steps
-    close(torch.tensor(lg), torch.tensor(le), f"recorded jk_gru step: losses of {steps} steps", tol=1e-4)
-    close(og.flat, oe.flat, f"recorded jk_gru step: parameters after {steps} steps", tol=1e-4)
-    assert not np.allclose(le[0], le[-1])
+    H.static_recorded_step_replays_on_the_table_kernels(_static_model, _paths(), "jk_gru")

@@ -4,48 +4,27 @@ and the library, the widths they serve, their argument checks (which return befo
 translation unit's kernels without scratch, the dispatch switch, the refusals of ``encode_rows`` and the layout check of
 ``PairBatches``."""
 import ctypes
-import os
 import re
-import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gcn-bmp_amd", "csrc")
+from table_build import BAD_TABLES, CSRC, P, bad_id, check_table_entries, enc_batch, header_args, lib, resource_usage
+
 STEP = ("bmp_jk_step_table_supported", "bmp_jk_step_table_fwd", "bmp_jk_step_table_bwd")
 MEAN = ("bmp_jk_mean_fwd", "bmp_jk_mean_bwd")
 
 
-def _lib():
-    import __graft_entry__ as g
-    g.build()
-    from bmp import _lib
-    return _lib
-
-
-def _header_args(name):
-    src = open(os.path.join(ROOT, "include", "bmp.h")).read()
-    m = re.search(r"\bint %s\s*\(([^;]*)\);" % name, src)
-    assert m, name
-    return [a.strip() for a in m.group(1).replace("\n", " ").split(",")]
-
-
 def test_header_and_ctypes_table_declare_the_entry_points():
-    _l = _lib()
+    _l = lib()
     from bmp import functional as Fn
     for name in STEP + MEAN:
-        args = _header_args(name)
+        args = header_args(name)
         assert name in _l.SIGNATURES, name
         assert len(args) == len(_l.SIGNATURES[name][1]), (name, len(args), len(_l.SIGNATURES[name][1]))   # one ctypes entry per argument
-    for name in STEP[1:]:
-        # the whole-tile list, then the table: mt_row0, mt_nblk, mt_rows, tile_stride in front of the stream
-        args, whole = _header_args(name), _header_args(name.replace("_table", "_tile"))
-        assert args[:len(whole) - 1] == whole[:-1] and args[-1] == whole[-1], name
-        assert [a.split()[-1].lstrip("*") for a in args[len(whole) - 1:-1]] == ["mt_row0", "mt_nblk", "mt_rows", "tile_stride"], name
-        assert _l.SIGNATURES[name][1][:len(whole) - 1] == _l.SIGNATURES[name.replace("_table", "_tile")][1][:-1]
-    kern = open(os.path.join(CSRC, "bmp_kernels.h")).read()
+    check_table_entries(STEP[1:])
+    kern = open(CSRC + "/bmp_kernels.h").read()
     for name in STEP + MEAN:
         assert re.search(r'extern "C" int %s\s*\(' % name, kern), name
     assert set(Fn.JK_TABLE_DEFAULT) == {(k, d) for k in ("jknet", "jk_gru") for d in (64, 128)}
@@ -54,14 +33,10 @@ def test_header_and_ctypes_table_declare_the_entry_points():
 
 
 def test_library_exports_the_entry_points_and_serves_64_and_128():
-    L = _lib().lib()
+    L = lib().lib()
     for name in STEP + MEAN:
         assert hasattr(L, name), name
     assert [d for d in (8, 16, 24, 32, 40, 64, 128, 256) if L.bmp_jk_step_table_supported(d)] == [64, 128]
-
-
-# Non-null, 16-byte aligned addresses nobody reads: every case below fails an argument check, which returns before any launch.
-P = 0x10000
 
 
 def _step_fwd(L, ng=1, d=64, r0=P, nb=P, rows=384, stride=0):
@@ -72,16 +47,15 @@ def _step_bwd(L, ng=1, d=64, r0=P, nb=P, rows=384, stride=0):
     return L.bmp_jk_step_table_bwd(ng, P, P, 3, d, P, P, P, P, None, P, P, P, r0, nb, rows, stride, None)
 
 
-@pytest.mark.parametrize("bad", [dict(r0=None), dict(nb=None), dict(rows=0), dict(stride=96), dict(stride=130), dict(ng=3),
-                                 dict(d=32)], ids=lambda b: "-".join(f"{k}={v}" for k, v in b.items()))
+@pytest.mark.parametrize("bad", BAD_TABLES + [dict(ng=3), dict(d=32)], ids=bad_id)
 def test_step_entries_check_their_arguments_before_any_launch(bad):
-    L = _lib().lib()
+    L = lib().lib()
     assert _step_fwd(L, **bad) < -1000
     assert _step_bwd(L, **bad) < -1000
 
 
 def test_mean_entries_check_their_arguments_before_any_launch():
-    L = _lib().lib()
+    L = lib().lib()
     nine = (ctypes.c_void_p * 9)(*([P] * 9))
     assert L.bmp_jk_mean_fwd(nine, 9, 32, 64, P, None) < -1000             # T = 9
     assert L.bmp_jk_mean_bwd(P, 9, 32, 64, nine, None) < -1000
@@ -97,16 +71,8 @@ def test_table_kernels_do_not_spill():
     """The table instances are the eight step kernels of their own translation unit: 2 directions x Nu = d and 2d x 2 widths,
     none with scratch, each within the 512 registers a SIMD's lane has for the two waves of a 512-thread workgroup; beside
     them the sixteen row-count 'mean' kernels (T = 1..8, two directions)."""
-    import __graft_entry__ as g
     with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([g._hipcc(), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", CSRC, "--cuda-device-only",
-                            "-c", os.path.join(CSRC, "bmp_jk_table.hip"), "-o", os.path.join(tmp, "jk_table.o"),
-                            "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    grab = lambda pat: [int(x) for x in re.findall(pat, r.stderr)]
-    scratch, vgpr, agpr, occ = grab(r"ScratchSize \[bytes/lane\]: (\d+)"), grab(r" VGPRs: (\d+)"), grab(r" AGPRs: (\d+)"), \
-        grab(r"Occupancy \[waves/SIMD\]: (\d+)")
+        names, scratch, vgpr, agpr, occ, _lds = resource_usage("bmp_jk_table.hip", tmp, "--cuda-device-only")
     assert len(names) == len(scratch) == len(vgpr) == len(agpr) == len(occ) == 8 + 16, names
     assert sum("table_fwd" in n for n in names) == 4 and sum("table_bwd" in n for n in names) == 4, names
     assert sum("k_jk_mean" in n for n in names) == 16, names
@@ -126,17 +92,11 @@ def _jkgru(**kw):
     return JKGruGGNN(out_dim=8, hidden_dim=64, n_layers=2, **kw)
 
 
-def _enc_batch():
-    from bmp import enclayout, packed, synth
-    store = synth.make_store(6, seed=2, n_lo=2, n_hi=20, n_mean=8)
-    return enclayout.encode_from_store(packed.MolStore(store), [np.array([0, 1, 2]), np.array([3, 4, 0])], dedup=True)
-
-
 def test_encoders_have_the_rows_pair_and_refuse_with_their_reasons():
     from bmp import ggnn_gate as G
     from bmp.ggnn import _StepEncoder
     from bmp.ggnn_jk import JK_ATTN_LAYOUT_REASON, JKGruGGNN, JKNetGGNN
-    eb = _enc_batch()
+    eb = enc_batch()
     for make in (lambda **kw: _jknet("max", **kw), lambda **kw: _jknet("mean", **kw), _jkgru, lambda **kw: _jkgru(self_loop=True, **kw)):
         enc = make()
         assert enc.eval().rows_reason() is None and enc.train().rows_reason() is None

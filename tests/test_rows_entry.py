@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_ggdev_enc_build import _enc_batch
+from table_build import enc_batch
 
 CONCAT = ("concat_hidden=True reads out after every step on the per-instance rows; it takes the per-instance "
           "batch form")
@@ -51,7 +51,7 @@ def _enc(name, **kw):
 
 def _pb():
     if "eb" not in _EB:
-        _EB["eb"] = _enc_batch()
+        _EB["eb"] = enc_batch()
     return _EB["eb"].pb_enc
 
 

@@ -11,13 +11,13 @@ import json
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "gcn-bmp_amd")]
+sys.path[:0] = [ROOT, os.path.join(ROOT, "gcn-bmp_amd"), os.path.join(ROOT, "tools")]
 from bmp import functional as Fn, packed, synth, _lib          # noqa: E402
 from bmp._lib import check, ptr, stream                        # noqa: E402
+from table_probe_lib import stats, timed_pair                  # noqa: E402
 
 
 def timed(fn, warm=5, reps=30):
@@ -29,28 +29,7 @@ def timed(fn, warm=5, reps=30):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(); fn(); b.record(); b.synchronize()
         ts.append(a.elapsed_time(b) * 1e3)
-    ts = np.array(ts)
-    return dict(median_us=float(np.median(ts)), min_us=float(ts.min()), p90_us=float(np.percentile(ts, 90)))
-
-
-def _stats(ts):
-    ts = np.array(ts)
-    return dict(median_us=float(np.median(ts)), min_us=float(ts.min()), p90_us=float(np.percentile(ts, 90)))
-
-
-def timed_pair(fa, fb, warm=10, reps=100):
-    """``timed`` for two forms of the same work, alternating them call by call: what else runs on the host and the card's clock
-    state meet both alike, and 100 calls of each make a window of seconds, not milliseconds."""
-    for _ in range(warm):
-        fa(); fb()
-    torch.cuda.synchronize()
-    ta, tb = [], []
-    for _ in range(reps):
-        for fn, ts in ((fa, ta), (fb, tb)):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(); fn(); b.record(); b.synchronize()
-            ts.append(a.elapsed_time(b) * 1e3)
-    return _stats(ta), _stats(tb)
+    return stats(ts)
 
 
 def main():

@@ -16,7 +16,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "gcn-bmp_amd"), os.path.join(ROOT, "tools")]
 from bmp import functional as Fn, packed, synth          # noqa: E402
-from gate_probe import timed_pair                        # noqa: E402
+from table_probe_lib import timed_pair                   # noqa: E402
 
 KINDS = (("jknet", 1, False), ("jk_gru", 2, False), ("jk_gru_loop", 2, True))
 

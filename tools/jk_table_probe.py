@@ -13,26 +13,25 @@ Report only: ms per replay of GraphedTrainStep at 32 pairs for a JKGruGGNN + Hol
 off (the composed chain a static batch ran before).
 
 The driver opens no GPU itself: every leg -- the step timing of one width, the replay timing of one width -- is a child process
-under a time limit of its own, and the first leg that fails or runs out of time ends the probe.  One JSON line per run, then one
+under a time limit of its own (tools/table_probe_lib.py), and the first leg that fails or runs out of time ends the probe.  One JSON line per run, then one
 summary line.
 python tools/jk_table_probe.py [--runs 4] [--out FILE]          (profiles/jk_table_probe.json)"""
 import json
 import os
-import subprocess
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "gcn-bmp_amd"), os.path.join(ROOT, "tools")]
+import table_probe_lib as T                                    # noqa: E402
 
-WIDTHS, LAYERS, B = (64, 128), 4, 1024
+WIDTHS, LAYERS = (64, 128), 4
 KINDS = {"jknet": (1, False), "jk_gru": (2, True)}            # Nu / d, self loop
-LEG_SECONDS = {"steps": 300, "replay": 180}
+# (the step leg of one width makes 4 alternating timings per run, 16 in four runs: 300 s since the probe's first profile)
+LEG_SECONDS = {"steps": 300, "replay": T.REPLAY_SECONDS}
 
 
 def step_run(Fn, pb, dev, d, ng, loop):
     import torch
-    from gate_probe import timed_pair
     N = pb.n_rows
     f = lambda *s: (torch.randn(*s, device=dev) * 0.1)
     x = f(N, d).requires_grad_()
@@ -45,34 +44,17 @@ def step_run(Fn, pb, dev, d, ng, loop):
         out = Fn.jk_step(x, *w, pb, fused)
         torch.autograd.grad(out, [x] + [t for t in w if t is not None], dout)
 
-    before = dict(Fn.JK_PATHS)
-    tf, tc = timed_pair(lambda: [step(l, True) for l in range(LAYERS)], lambda: [step(l, False) for l in range(LAYERS)])
-    took = {a: Fn.JK_PATHS[a] - before[a] for a in before}
-    assert took["fused"] == took["composed"] == 110 * LAYERS, took          # the two forms really ran
-    tf, tc = ({a: b / LAYERS for a, b in t.items()} for t in (tf, tc))
-    gain = tc["median_us"] - tf["median_us"]
-    spread = (tf["p90_us"] - tf["median_us"]) + (tc["p90_us"] - tc["median_us"])
-    return dict(table=tf, composed=tc, gain_us=gain, spreads_us=spread, passes=bool(gain > spread))
-
-
-def _world():
-    import torch
-    from bmp import packed, synth
-    dev = torch.device("cuda:0")
-    store = synth.make_store(544, seed=2018)
-    i1, i2, lab = synth.make_pairs(544, seed=777, limit=B)
-    return dev, packed.DeviceMolStore(packed.MolStore(store), dev), i1, i2, lab.reshape(-1, 1)
+    return T.table_against_composed(Fn.JK_PATHS, step, LAYERS)
 
 
 def leg_steps(d, runs):
     """One JSON line per run: the step of both kinds at width ``d`` in both table layouts."""
-    from bmp import enclayout, functional as Fn
-    dev, ds, i1, i2, _lab = _world()
-    batches = {"encoder": enclayout.encode_from_store_device(ds, [i1, i2]),
-               "encoder_dedup": enclayout.encode_from_store_device(ds, [i1, i2], dedup=True)}
+    from bmp import functional as Fn
+    dev, ds, i1, i2, _lab = T.world()
+    batches = T.table_batches(ds, i1, i2)
     Fn.JK_TABLE_DEFAULT.update({k: True for k in Fn.JK_TABLE_DEFAULT})      # "table" means the kernels here, whatever the default says
     for run in range(runs):
-        res = dict(run=run, d=d, pairs=B, layers=LAYERS)
+        res = dict(run=run, d=d, pairs=T.B, layers=LAYERS)
         for kind, (ng, loop) in KINDS.items():
             for name, eb in batches.items():
                 res[f"{kind}_{name}"] = dict(rows=eb.pb_enc.n_rows, tiles=eb.pb_enc.n_mtiles, **step_run(Fn, eb.pb_enc, dev, d, ng, loop))
@@ -82,66 +64,28 @@ def leg_steps(d, runs):
 def leg_replay(d):
     """One JSON line: ms per replay of the recorded JKGruGGNN training step at 32 pairs (load + replay, 200 of them after 20),
     with the switch off and on."""
-    import numpy as np
     import torch
-    from bmp import functional as Fn, packed
-    from bmp.dp import FlatAdam, GraphedTrainStep
+    from bmp import functional as Fn
     from bmp.ggnn_jk import JKGruGGNN
     from bmp.predictor import GraphConvPredictorForPair, build_link_predictor
-    dev, ds, i1, i2, lab = _world()
+    dev, ds, i1, i2, lab = T.world()
     res = dict(replay32_jk_gru=True, d=d)
     for table in (False, True):
         Fn.JK_TABLE_DEFAULT.update({k: table for k in Fn.JK_TABLE_DEFAULT})
         torch.manual_seed(1)
         enc = JKGruGGNN(16, d, LAYERS, weight_tying=False, update_tying=False, self_loop=True)
         model = GraphConvPredictorForPair(enc, None, build_link_predictor("hole", 16, 1)).to(dev)
-        opt = FlatAdam(model, alpha=1e-3)
-        sb = packed.StaticPairBatch(ds, 32)
-        stepper = GraphedTrainStep(model, opt)
-        before = dict(Fn.JK_PATHS)
-        ts = []
-        for k in range(220):
-            sl = slice(32 * (k % 32), 32 * (k % 32) + 32)
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            sb.load([i1[sl], i2[sl]], lab[sl]); stepper(sb); torch.cuda.synchronize()
-            if k >= 20:
-                ts.append((time.perf_counter() - t0) * 1e3)
-        took = {a: Fn.JK_PATHS[a] - before[a] for a in before}
-        assert (took["composed"] == 0) == table and (took["fused"] == 0) != table, (table, took)      # what was recorded
-        res["table" if table else "composed"] = dict(median_ms=float(np.median(ts)), min_ms=float(np.min(ts)),
-                                                     p90_ms=float(np.percentile(ts, 90)))
+        res["table" if table else "composed"] = T.replay_ms(Fn.JK_PATHS, ds, i1, i2, lab, model, table)
     print(json.dumps(res), flush=True)
 
 
-def _child(leg, d, runs):
-    """Runs one leg as a process of its own under its time limit; its JSON lines, or None where it failed or ran out of time."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", leg, "--d", str(d), "--runs", str(runs)]
-    try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=LEG_SECONDS[leg])
-    except subprocess.TimeoutExpired:
-        print(json.dumps(dict(error=f"leg {leg} d={d}: no end within {LEG_SECONDS[leg]} s")), flush=True)
-        return None
-    if r.returncode != 0:
-        print(json.dumps(dict(error=f"leg {leg} d={d}: exit status {r.returncode}", tail=r.stderr[-1500:])), flush=True)
-        return None
-    return [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
-
-
 def main():
-    runs = int(sys.argv[sys.argv.index("--runs") + 1]) if "--runs" in sys.argv else 4
-    if "--leg" in sys.argv:
-        leg, d = sys.argv[sys.argv.index("--leg") + 1], int(sys.argv[sys.argv.index("--d") + 1])
-        return leg_steps(d, runs) if leg == "steps" else leg_replay(d)
-    lines = []
-    for leg in ("steps", "replay"):
-        for d in WIDTHS:
-            got = _child(leg, d, runs)
-            if got is None:
-                return 1                                 # nothing more is started on the card behind a failed leg
-            for l in got:
-                print(json.dumps(l), flush=True)
-            lines += got
+    runs = int(T.arg("--runs", 4))
+    if T.arg("--leg"):
+        return leg_steps(int(T.arg("--d")), runs) if T.arg("--leg") == "steps" else leg_replay(int(T.arg("--d")))
+    lines = T.run_legs(__file__, [(leg, d, LEG_SECONDS[leg]) for leg in ("steps", "replay") for d in WIDTHS], runs)
+    if lines is None:
+        return 1
     need = 3 if runs >= 4 else runs
     layouts = ("encoder", "encoder_dedup")
     steps = [l for l in lines if "run" in l]
@@ -149,12 +93,7 @@ def main():
               for kind in KINDS for d in WIDTHS}
     adopt = {k: bool(min(v.values()) >= need) for k, v in passes.items()}
     summary = dict(summary=True, runs=runs, passes=passes, adopt=adopt)
-    lines.append(summary)
-    print(json.dumps(summary), flush=True)
-    if "--out" in sys.argv:
-        with open(sys.argv[sys.argv.index("--out") + 1], "w") as fh:
-            for l in lines:
-                fh.write(json.dumps(l) + "\n")
+    T.finish(lines, summary)
     return 0
 
 
