@@ -69,6 +69,15 @@ SIGNATURES = {
     "bmp_nfp_readout_tile_supported": (_I, [_I, _I]),
     "bmp_nfp_readout_tile_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "bmp_nfp_readout_tile_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "bmp_nfp_layer_table_supported": (_I, [_I]),
+    "bmp_nfp_readout_table_supported": (_I, [_I, _I]),
+    "bmp_nfp_layer_table_fwd": (_I, [_P, _I, _I] + [_P] * 9 + [_P, _P, _I, _I, _P]),
+    "bmp_nfp_layer_table_bwd": (_I, [_P, _P, _I, _I] + [_P] * 9 + [_P, _P, _I, _I, _P]),
+    "bmp_nfp_readout_table_fwd": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P]),
+    "bmp_nfp_readout_table_bwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _Z, _P, _P, _I, _I, _P]),
+    "bmp_nfp_rows_enc": (_I, [_P, _P, _P, _I, _P, _P, _P, _P]),
+    "bmp_nfp_inst_expand": (_I, [_P, _P, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "bmp_nfp_inst_reduce": (_I, [_P, _I, _P, _P, _I, _P, _P]),
     "bmp_gin_layer_supported": (_I, [_I]),
     "bmp_gin_layer_tile_fwd": (_I, [_P, _I, _I] + [_P] * 12),
     "bmp_gin_layer_tile_bwd": (_I, [_P, _P, _P, _P, _I, _I] + [_P] * 9),

@@ -945,7 +945,7 @@ class PRelLayerFn(Function):
 
 # ---------------------------------------------------------------------------------------------------------
 # Neural-fingerprint encoder (models/models/nfp.py; csrc/bmp_nfp.hip).  ``nd`` is the batch's derived NFP data
-# (bmp.nfp.nfp_derived): self_w, deg_class, deg_rows, deg_cnt.
+# (bmp.nfp.nfp_derived): self_w, deg_class, deg_rows, deg_cnt, bwd_w.  On the tile-table seam further down (_table_ok, _table_args).
 # ---------------------------------------------------------------------------------------------------------
 def whole_tiles_ok(pb) -> bool:
     """The fused GIN and NFP kernels take whole 128-row tiles whose molecules never straddle a tile."""
@@ -953,12 +953,44 @@ def whole_tiles_ok(pb) -> bool:
 
 
 NFP_PATHS = {"layer_tile": 0, "layer_rows": 0, "readout_tile": 0, "readout_rows": 0}      # forward calls per kernel form
+# ... and the layer's forward calls on any batch form as the table families count theirs: the whole-tile and the table kernels
+# are "fused" (in NFP_PATHS both count as layer_tile / readout_tile), the row-wise kernels "composed"
+NFP_LAYER_PATHS = {"fused": 0, "composed": 0}
+# On a tile table (the encoder layout, with or without dedup, and the fixed-shape batch): the widths whose table kernels (csrc/
+# bmp_nfp_table.hip) beat the row-wise kernels by the project's rule -- by more than the two forms' p90 - median spreads together
+# in at least three of four runs on the 1024-pair DDI-shaped batch, in BOTH table layouts, for the layer (forward + backward +
+# weight gradient) AND for the readout (tools/nfp_table_probe.py, profiles/nfp_table_probe.json).  A width set to
+# False here keeps the row-wise kernels on table batches, its kernels reachable by setting the entry.  Measured: both widths pass
+# in 4 of 4 runs in both layouts, layer and readout (layer d = 64: 173 against 263 us without dedup, 138 against 195 us with it;
+# d = 128: 268 against 583 us and 171 against 298 us; readout d = o = 64: 169 against 446 us and 168 against 180 us, bound by the
+# host there; d = o = 128: 170 against 525 us and 97 against 224 us).
+NFP_TABLE_DEFAULT = {64: True, 128: True}
+
+
+def nfp_table_ok(pb, d: int, o: int = None) -> bool:
+    """The batch carries a tile table that the NFP layer's table kernels (``o``: the readout's) take."""
+    L = _lib.lib()
+    ok = L.bmp_nfp_layer_table_supported(int(d)) if o is None else L.bmp_nfp_readout_table_supported(int(d), int(o))
+    return _table_ok(pb) and pb.row_mol is not None and bool(ok)
+
+
+def _pack_k4_classes(W: torch.Tensor) -> torch.Tensor:
+    """``pack_k4`` of each of the seven class matrices [7 x K x N] in one copy: [7][K/4][N][4]."""
+    C, K, N = W.shape
+    return W.detach().reshape(C, K // 4, 4, N).permute(0, 1, 3, 2).contiguous()
+
+
+def _nfp_entry(kind, tile, table, direction):
+    """The C entry of an NFP layer or readout call: whole tiles, a tile table or rows."""
+    return f"bmp_nfp_{kind}_{'tile_' if tile else 'table_' if table else ''}{direction}"
 
 
 class NFPLayerFn(Function):
     """NFPUpdate.__call__ (nfp.py:36-62): out = sigmoid(fv . W_deg + B), fv = adj . h.  WT [7 x d_in x d_out] (K-major per
     degree class), B [d_out] = the sum of the seven biases.  ``fused``: the per-tile MFMA kernels and the listed MFMA weight
-    gradient where the shape allows (d_in == d_out in {64, 128}, whole tiles); False: the row-wise kernels at every width."""
+    gradient where the shape allows (d_in == d_out in {64, 128}, whole tiles, or a tile table at the widths NFP_TABLE_DEFAULT
+    holds True for: the grid is the table's pb.n_mtiles entries, and with no gradient asked for the table kernel keeps no fv);
+    False: the row-wise kernels at every width.  ``nd["bwd_w"]``: the rows whose zeros leave the backward without gradient."""
 
     @staticmethod
     def forward(ctx, x, WT, B, pb, nd, fused):
@@ -970,22 +1002,27 @@ class NFPLayerFn(Function):
             raise ValueError("nfp layer: weight shapes do not match x")
         d_out = WT.shape[2]
         WT = WT.contiguous(); B = B.contiguous()
-        fv = torch.empty(N, d_in, dtype=torch.float32, device=x.device)
         out = torch.empty(N, d_out, dtype=torch.float32, device=x.device)
         tile = (bool(fused) and whole_tiles_ok(pb) and pb.row_mol is not None and d_in == d_out
                 and bool(L.bmp_nfp_layer_supported(d_in)))
-        if tile:
-            WTp = torch.stack([pack_k4(WT[k]) for k in range(7)])
-            check(L.bmp_nfp_layer_tile_fwd(ptr(x), pb.n_tiles, d_in, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
-                                           ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(WTp), ptr(B), ptr(fv), ptr(out), stream()),
-                  "bmp_nfp_layer_tile_fwd")
+        table = bool(fused) and d_in == d_out and NFP_TABLE_DEFAULT.get(d_in, False) and nfp_table_ok(pb, d_in)
+        # forward-only evaluation (no input needs a gradient): the table kernel stores no fv
+        infer = table and not any(ctx.needs_input_grad)
+        fv = None if infer else torch.empty(N, d_in, dtype=torch.float32, device=x.device)
+        name = _nfp_entry("layer", tile, table, "fwd")
+        if tile or table:
+            WTp = _pack_k4_classes(WT)
+            check(getattr(L, name)(ptr(x), pb.n_mtiles if table else pb.n_tiles, d_in, ptr(pb.csr_ptr), ptr(pb.csr_col),
+                                   ptr(pb.csr_val), ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(WTp), ptr(B), ptr(fv), ptr(out),
+                                   *_table_args(pb, table), stream()), name)
         else:
             check(L.bmp_nfp_layer_fwd(ptr(x), pb.n_tiles, d_in, d_out, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val),
-                                      ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(WT), ptr(B), ptr(fv), ptr(out), stream()),
-                  "bmp_nfp_layer_fwd")
-        ctx.save_for_backward(WT, fv, out)
-        ctx.pb, ctx.nd, ctx.listed, ctx.tile = pb, nd, int(bool(fused)), tile
-        NFP_PATHS["layer_tile" if tile else "layer_rows"] += 1
+                                      ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(WT), ptr(B), ptr(fv), ptr(out), stream()), name)
+        if not infer:
+            ctx.save_for_backward(WT, fv, out)
+        ctx.pb, ctx.nd, ctx.listed, ctx.tile, ctx.table = pb, nd, int(bool(fused)), tile, table
+        NFP_PATHS["layer_tile" if tile or table else "layer_rows"] += 1
+        NFP_LAYER_PATHS["fused" if tile or table else "composed"] += 1
         return out
 
     @staticmethod
@@ -997,19 +1034,22 @@ class NFPLayerFn(Function):
         N, d_in = fv.shape
         d_out = out.shape[1]
         dev = fv.device
-        Wnat = WT.transpose(1, 2).contiguous()
         f = lambda *s_: torch.empty(*s_, dtype=torch.float32, device=dev)
         dpre, dh = f(N, d_out), f(N, d_in)
-        if ctx.tile:
-            Wnp = torch.stack([pack_k4(Wnat[k]) for k in range(7)])
-            check(L.bmp_nfp_layer_tile_bwd(ptr(dout), ptr(out), pb.n_tiles, d_in, ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val),
-                                           ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(pb.row_w), ptr(Wnp), ptr(dpre), ptr(dh),
-                                           stream()), "bmp_nfp_layer_tile_bwd")
+        table = ctx.table
+        name = _nfp_entry("layer", ctx.tile, table, "bwd")
+        if ctx.tile or table:
+            # pack_k4 of every W_k = WT[k]^T, straight from WT in one copy: Wnp[k][a][n][b] = WT[k][n][4 a + b]
+            Wnp = WT.detach().reshape(7, d_in, d_out // 4, 4).permute(0, 2, 1, 3).contiguous()
+            check(getattr(L, name)(ptr(dout), ptr(out), pb.n_mtiles if table else pb.n_tiles, d_in, ptr(pb.csrT_ptr),
+                                   ptr(pb.csrT_col), ptr(pb.csrT_val), ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(nd["bwd_w"]),
+                                   ptr(Wnp), ptr(dpre), ptr(dh), *_table_args(pb, table), stream()), name)
         else:
             dfv = f(N, d_in)
+            Wnat = WT.transpose(1, 2).contiguous()
             check(L.bmp_nfp_layer_bwd(ptr(dout), ptr(out), pb.n_tiles, d_in, d_out, ptr(pb.csrT_ptr), ptr(pb.csrT_col),
-                                      ptr(pb.csrT_val), ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(pb.row_w), ptr(Wnat), ptr(dpre),
-                                      ptr(dfv), ptr(dh), stream()), "bmp_nfp_layer_bwd")
+                                      ptr(pb.csrT_val), ptr(nd["self_w"]), ptr(nd["deg_class"]), ptr(nd["bwd_w"]), ptr(Wnat),
+                                      ptr(dpre), ptr(dfv), ptr(dh), stream()), name)
         dWT, dB = f(7, d_in, d_out), f(d_out)
         nws = L.bmp_nfp_layer_wgrad_ws_floats(N, d_in, d_out)
         ws = _ws(nws, dev)
@@ -1042,16 +1082,18 @@ class NFPReadoutFn(Function):
             g = g_prev
             ctx.mark_dirty(g_prev)
         tile = bool(fused) and whole_tiles_ok(pb) and pb.row_mol is not None and bool(L.bmp_nfp_readout_tile_supported(d, o))
+        table = bool(fused) and NFP_TABLE_DEFAULT.get(d, False) and nfp_table_ok(pb, d, o)
         acc = 0 if g_prev is None else 1
-        if tile:
-            check(L.bmp_nfp_readout_tile_fwd(ptr(h), pb.n_tiles, d, o, ptr(pack_k4(WT)), ptr(b), ptr(pb.row_w), ptr(pb.row_mol),
-                                             ptr(s), ptr(g), acc, stream()), "bmp_nfp_readout_tile_fwd")
+        name = _nfp_entry("readout", tile, table, "fwd")
+        if tile or table:
+            check(getattr(L, name)(ptr(h), pb.n_mtiles if table else pb.n_tiles, d, o, ptr(pack_k4(WT)), ptr(b), ptr(pb.row_w),
+                                   ptr(pb.row_mol), ptr(s), ptr(g), acc, *_table_args(pb, table), stream()), name)
         else:
             check(L.bmp_nfp_readout_fwd(ptr(h), pb.n_tiles, d, o, ptr(WT), ptr(b), ptr(pb.row_w), ptr(pb.mol_row0), ptr(pb.mol_nrows),
-                                        pb.n_mols, ptr(s), ptr(g), acc, stream()), "bmp_nfp_readout_fwd")
+                                        pb.n_mols, ptr(s), ptr(g), acc, stream()), name)
         ctx.save_for_backward(h, WT, s)
-        ctx.pb, ctx.has_prev, ctx.tile = pb, g_prev is not None, tile
-        NFP_PATHS["readout_tile" if tile else "readout_rows"] += 1
+        ctx.pb, ctx.has_prev, ctx.tile, ctx.table = pb, g_prev is not None, tile, table
+        NFP_PATHS["readout_tile" if tile or table else "readout_rows"] += 1
         return g
 
     @staticmethod
@@ -1071,14 +1113,50 @@ class NFPReadoutFn(Function):
         db = torch.empty(o, dtype=torch.float32, device=dev)
         nws = L.bmp_nfp_readout_bwd_ws_floats(N, d, o)
         ws = _ws(nws, dev)
-        if ctx.tile:
-            check(L.bmp_nfp_readout_tile_bwd(ptr(dg), ptr(h), ptr(s), pb.n_tiles, d, o, ptr(pack_k4(Wnat)), ptr(pb.row_w),
-                                             ptr(pb.row_mol), ptr(dh), ptr(dWT), ptr(db), ptr(ws), nws, stream()),
-                  "bmp_nfp_readout_tile_bwd")
+        table = ctx.table
+        name = _nfp_entry("readout", ctx.tile, table, "bwd")
+        if ctx.tile or table:
+            check(getattr(L, name)(ptr(dg), ptr(h), ptr(s), pb.n_mtiles if table else pb.n_tiles, d, o, ptr(pack_k4(Wnat)),
+                                   ptr(pb.row_w), ptr(pb.row_mol), ptr(dh), ptr(dWT), ptr(db), ptr(ws), nws, *_table_args(pb, table),
+                                   stream()), name)
         else:
             check(L.bmp_nfp_readout_bwd(ptr(dg), ptr(h), ptr(s), pb.n_tiles, d, o, ptr(Wnat), ptr(pb.row_w), ptr(pb.row_mol), ptr(dh),
-                                        ptr(dWT), ptr(db), ptr(ws), nws, stream()), "bmp_nfp_readout_bwd")
+                                        ptr(dWT), ptr(db), ptr(ws), nws, stream()), name)
         return dh, dWT, db, None, (dg if ctx.has_prev else None), None
+
+
+class NFPInstFn(Function):
+    """The NFP readout of a batch in the encoder layout, per instance: g_inst[i] = g_real[uid[i]] + padcount[i] * pad
+    (bmp.nfp.inst_readout_host is the host form).  g_real [U x o]: the readout over the real atoms of every encoded molecule;
+    pad [o]: what one padded position adds, summed over the layers; padcount: row_w at the instance's pad row.  The backward sums
+    the instances of an encoded molecule in the order of eb.uptr / eb.uinst (bmp_nfp_inst_reduce): no atomics, bit-equal from run
+    to run."""
+
+    @staticmethod
+    def forward(ctx, g_real, pad, eb):
+        L = _lib.lib()
+        U, o = g_real.shape
+        pb = eb.pb
+        if U != eb.n_encoded or tuple(pad.shape) != (o,):
+            raise ValueError("nfp instance readout: g_real must hold one row per encoded molecule and pad one entry per channel")
+        g_real, pad = g_real.contiguous(), pad.contiguous()
+        g = torch.empty(pb.n_mols, o, dtype=torch.float32, device=g_real.device)
+        check(L.bmp_nfp_inst_expand(ptr(g_real), ptr(pad), o, ptr(eb.uid), ptr(pb.row_w), ptr(pb.mol_row0), ptr(pb.mol_nrows),
+                                    pb.n_mols, ptr(g), stream()), "bmp_nfp_inst_expand")
+        ctx.eb, ctx.U = eb, U
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        L = _lib.lib()
+        eb = ctx.eb
+        pb = eb.pb
+        dg = dg.contiguous()
+        o = dg.shape[1]
+        dg_real = torch.empty(ctx.U, o, dtype=torch.float32, device=dg.device)
+        check(L.bmp_nfp_inst_reduce(ptr(dg), o, ptr(eb.uptr), ptr(eb.uinst), ctx.U, ptr(dg_real), stream()), "bmp_nfp_inst_reduce")
+        padcount = pb.row_w[pb.mol_row0.long() + pb.mol_nrows.long() - 1]
+        return dg_real, (dg * padcount[:, None]).sum(dim=0), None
 
 
 # ---------------------------------------------------------------------------------------------------------

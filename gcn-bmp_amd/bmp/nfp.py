@@ -11,6 +11,12 @@ reproduces that, as it does for GGNN.
 Per-batch derivations (``nfp_derived``): ``self_w`` [N] f32, ``deg_class`` [N] int32 in 0..7, and the row lists by degree
 class ``deg_rows`` [7 x N] / ``deg_cnt`` [7].  Device batches get them from csrc/bmp_nfp.hip; the numpy versions below are
 pinned against those bit for bit (tests/test_gpu_nfp.py) and serve host batches (CPU tests of the layout).
+
+Batch forms: per instance and the fixed-shape batch (``PairBatches(layout="static")``) through ``forward``; the encoder layout,
+with or without ``dedup``, through ``encode_rows`` / ``readout_enc``: layers AND readout run on the encoder rows, and an instance's
+padded positions enter its molecule vector as padcount * ``pad_term()`` (tests/test_nfp_table_build.py pins the formula against
+the dense restatement in float64).  At d = 64 / 128 the layers and readouts of a table batch run on the tile-table kernels
+(csrc/bmp_nfp_table.hip, ``Fn.NFP_TABLE_DEFAULT``).
 """
 from __future__ import annotations
 
@@ -39,16 +45,21 @@ def deg_class_of(deg: np.ndarray) -> np.ndarray:
     return cls
 
 
-def nfp_rows_host(pb: PackedMolBatch):
+def nfp_rows_host(pb: PackedMolBatch, enc: bool = False):
     """(self_w [N] float32, deg_class [N] int32) of a batch packed from the store, in numpy: the diagonal of the NFP
     adjacency is 1 on the real atoms of every molecule (rows mol_row0 .. mol_row0 + mol_nrows - 2) and 0 on its pad row and
-    on dead rows; the degree is self_w plus the row's transposed-CSR values, added in entry order in float32."""
+    on dead rows; the degree is self_w plus the row's transposed-CSR values, added in entry order in float32.
+    ``enc``: the batch is in the encoder layout (``EncBatch.pb_enc``), where mol_nrows counts real atoms only and row_mol is
+    u >= 0 on a real atom, <= -2 on a tile's pad row, -1 on a dead row: self_w is 1 exactly where row_mol >= 0."""
     N = pb.n_rows
     row0 = pb.mol_row0.cpu().numpy().astype(np.int64)
     nrows = pb.mol_nrows.cpu().numpy().astype(np.int64)
-    self_w = np.zeros(N, dtype=np.float32)
-    for r0, n in zip(row0, nrows):
-        self_w[r0:r0 + n - 1] = 1.0
+    if enc:
+        self_w = (pb.row_mol.cpu().numpy() >= 0).astype(np.float32)
+    else:
+        self_w = np.zeros(N, dtype=np.float32)
+        for r0, n in zip(row0, nrows):
+            self_w[r0:r0 + n - 1] = 1.0
     ptrT = pb.csrT_ptr.cpu().numpy().astype(np.int64)
     valT = pb.csrT_val.cpu().numpy().astype(np.float32)
     deg = self_w.copy()
@@ -71,15 +82,24 @@ def deg_rows_host(deg_class: np.ndarray):
     return idx, cnt
 
 
-def nfp_derived(pb: PackedMolBatch) -> dict:
+def nfp_derived(pb: PackedMolBatch, enc: bool = False) -> dict:
     """The batch's NFP data, derived once and kept with the batch (``StaticPairBatch.reset_derived`` forgets it with the
-    other derived data): self_w, deg_class, deg_rows [7 x N], deg_cnt [7].  A batch made by ``pack_nfp_dense`` brings its
-    self_w / deg_class along as fields of the batch (taken from the dense array as given)."""
+    other derived data): self_w, deg_class, deg_rows [7 x N], deg_cnt [7] and bwd_w [N], the weight whose zeros the layer
+    backward leaves without gradient.  A batch made by ``pack_nfp_dense`` brings its self_w / deg_class along as fields of
+    the batch (taken from the dense array as given).
+    ``enc``: the caller says that ``pb`` is an ``EncBatch.pb_enc`` (``nfp_rows_host``); it is not guessed from the arrays.
+    There bwd_w is the liveness weight, 1 where row_mol != -1: the pad rows have row_w == 0 and still carry the gradient
+    that a co-attention sends back through ``EncRowsFn``.  On a per-instance batch bwd_w is row_w itself."""
     nd = pb._cache.get("nfp")
     if nd is not None:
+        if nd["enc"] != bool(enc):
+            raise ValueError("nfp_derived: this batch's NFP data was derived under the other row convention")
         return nd
     N, dev = pb.n_rows, pb.atom_id.device
     given = None if pb.nfp_self_w is None else (pb.nfp_self_w.to(dev), pb.nfp_deg_class.to(dev))
+    if enc and (given is not None or pb.row_mol is None):
+        raise ValueError("nfp_derived: an encoder-layout batch carries row_mol and no dense self_w / deg_class")
+    bwd_w = pb.row_w
     if pb.atom_id.is_cuda:
         from . import _lib
         from ._lib import check, ptr, stream
@@ -91,8 +111,13 @@ def nfp_derived(pb: PackedMolBatch) -> dict:
                 raise ValueError("NFP needs the batch's row -> molecule map (row_mol)")
             self_w = torch.empty(N, dtype=torch.float32, device=dev)
             deg_class = torch.empty(N, dtype=torch.int32, device=dev)
-            check(L.bmp_nfp_rows(ptr(pb.csrT_ptr), ptr(pb.csrT_val), ptr(pb.row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), N,
-                                 ptr(self_w), ptr(deg_class), stream()), "bmp_nfp_rows")
+            if enc:
+                bwd_w = torch.empty(N, dtype=torch.float32, device=dev)
+                check(L.bmp_nfp_rows_enc(ptr(pb.csrT_ptr), ptr(pb.csrT_val), ptr(pb.row_mol), N, ptr(self_w), ptr(deg_class),
+                                         ptr(bwd_w), stream()), "bmp_nfp_rows_enc")
+            else:
+                check(L.bmp_nfp_rows(ptr(pb.csrT_ptr), ptr(pb.csrT_val), ptr(pb.row_mol), ptr(pb.mol_row0), ptr(pb.mol_nrows), N,
+                                     ptr(self_w), ptr(deg_class), stream()), "bmp_nfp_rows")
         idx = torch.empty(NUM_DEGREE_TYPE * N, dtype=torch.int32, device=dev)
         cnt = torch.empty(NUM_DEGREE_TYPE, dtype=torch.int32, device=dev)
         ws = torch.empty(max(int(L.bmp_nfp_deg_rows_ws_ints(N)), 8), dtype=torch.int32, device=dev)
@@ -101,13 +126,27 @@ def nfp_derived(pb: PackedMolBatch) -> dict:
         if given is not None:
             self_w, deg_class = given
         else:
-            sw, dc = nfp_rows_host(pb)
+            sw, dc = nfp_rows_host(pb, enc)
             self_w, deg_class = torch.from_numpy(sw), torch.from_numpy(dc)
+            if enc:
+                bwd_w = (pb.row_mol != -1).to(torch.float32)
         i, c = deg_rows_host(deg_class.numpy())
         idx, cnt = torch.from_numpy(i.reshape(-1)), torch.from_numpy(c)
-    nd = dict(self_w=self_w, deg_class=deg_class, deg_rows=idx, deg_cnt=cnt)
+    nd = dict(self_w=self_w, deg_class=deg_class, deg_rows=idx, deg_cnt=cnt, bwd_w=bwd_w, enc=bool(enc))
     pb._cache["nfp"] = nd
     return nd
+
+
+def pad_count(eb) -> torch.Tensor:
+    """[I] float32: the padded positions of every instance of an ``EncBatch`` -- row_w at the pad row of its per-instance rows."""
+    pb = eb.pb
+    return pb.row_w[pb.mol_row0.long() + pb.mol_nrows.long() - 1]
+
+
+def inst_readout_host(g_real: torch.Tensor, pad: torch.Tensor, eb) -> torch.Tensor:
+    """Reference semantics of bmp_nfp_inst_expand (``Fn.NFPInstFn``) on host tensors: g_inst[i] = g_real[uid[i]] + padcount[i]
+    * pad, with g_real [U x o] the readout over the REAL atoms of every encoded molecule and pad [o] ``NFP.pad_term()``."""
+    return g_real[eb.uid.long()] + pad_count(eb).to(g_real.dtype)[:, None] * pad
 
 
 def pack_nfp_dense(atom_arrays: Sequence[np.ndarray], adjs: Sequence[np.ndarray], R: int = DEFAULT_R,
@@ -193,10 +232,14 @@ class NFPUpdate(nn.Module):
         self.graph_linears = nn.ModuleList([Linear(in_channels, out_channels) for _ in range(max_degree + 1)])
         self.max_degree, self.in_channels, self.out_channels = max_degree, in_channels, out_channels
 
-    def forward(self, h, pb: PackedMolBatch):
+    def bias_sum(self):
+        """B: every GraphLinear adds its bias to every row."""
+        return torch.stack([lin.b for lin in self.graph_linears]).sum(dim=0)
+
+    def forward(self, h, pb: PackedMolBatch, enc: bool = False):
+        """``enc``: ``pb`` is an ``EncBatch.pb_enc`` (``nfp_derived``)."""
         WT = torch.stack([lin.W.t() for lin in self.graph_linears])               # [7 x d_in x d_out]
-        B = torch.stack([lin.b for lin in self.graph_linears]).sum(dim=0)          # every GraphLinear adds its bias to every row
-        return Fn.NFPLayerFn.apply(h, WT, B, pb, nfp_derived(pb), self._fused)
+        return Fn.NFPLayerFn.apply(h, WT, self.bias_sum(), pb, nfp_derived(pb, enc), self._fused)
 
 
 class NFPReadout(nn.Module):
@@ -215,6 +258,7 @@ class NFPReadout(nn.Module):
         return Fn.NFPReadoutFn.apply(h, self.output_weight.W.t(), self.output_weight.b, pb, g_prev, self._fused)
 
 
+
 class NFP(nn.Module):
     """models/models/nfp.py:94-179."""
 
@@ -230,6 +274,7 @@ class NFP(nn.Module):
         self.out_dim, self.hidden_dim, self.max_degree = out_dim, hidden_dim, max_degree
         self.num_degree_type, self.n_layers, self.concat_hidden = max_degree + 1, n_layers, concat_hidden
         self.atoms = None
+        self._enc = None        # (g_real, pad term) between encode_rows and readout_enc
 
     def plannable(self) -> bool:
         return False            # no layout plan: FlatAdam / fit leave the encoder to autograd (bmp/dp.py)
@@ -248,6 +293,43 @@ class NFP(nn.Module):
             g = readout(h, pb, g)
         self.atoms = PackedAtoms(h, pb, 0 if pb.dense_map is not None else None)
         return g
+
+    def encode_rows(self, pb: PackedMolBatch):
+        """The encoder on the rows of an ``EncBatch.pb_enc`` (bmp/enclayout.py), layers AND per-layer readout: returns
+        (h_last, None).  The readout there sums over the REAL atoms of every encoded molecule (the pad rows have row_w == 0, no
+        molecule owns them); ``readout_enc``, the partner call, adds every instance's padded positions from the parameters alone."""
+        if _is_float_atoms(pb):
+            raise NotImplementedError("float atom features (embedding bypass, models/models/nfp.py:146-147) are not supported")
+        if not isinstance(pb, PackedMolBatch) or pb.mt_row0 is None or pb.row_mol is None:
+            raise ValueError("NFP.encode_rows takes the encoder layout of an EncBatch (pb_enc)")
+        if not pb.atom_id.is_cuda:
+            raise RuntimeError("NFP runs on the GPU only: there is no CPU path (move the model and the batch to the device)")
+        pb.check_atom_ids(self.embed.W.shape[0])
+        h = Fn.EmbedFn.apply(self.embed.W, pb.atom_id)
+        g = None
+        for update, readout in zip(self.layers, self.read_out_layers):
+            h = update(h, pb, enc=True)
+            g = readout(h, pb, g)
+        self._enc = (g, self.pad_term())
+        return h, None
+
+    def pad_term(self):
+        """[o]: what ONE padded position adds to a molecule's readout, summed over the layers.  Atom id 0, an empty adjacency row
+        and column and degree class 0 leave layer l as sigmoid(B_l) whatever the molecule and whatever h was before, so its term is
+        softmax(sigmoid(B_l) . Wo_l^T + bo_l): a function of the parameters alone, plain torch on o-vectors for all layers at once
+        (no BLAS call: a fixed order), differentiable."""
+        B = torch.stack([up.bias_sum() for up in self.layers])                                # [L x d]
+        Wo = torch.stack([ro.output_weight.W for ro in self.read_out_layers])                 # [L x o x d]
+        bo = torch.stack([ro.output_weight.b for ro in self.read_out_layers])                 # [L x o]
+        return torch.softmax((Wo * torch.sigmoid(B)[:, None, :]).sum(dim=2) + bo, dim=1).sum(dim=0)
+
+    def readout_enc(self, eb):
+        """The molecule vector of every INSTANCE of the ``EncBatch`` whose ``pb_enc`` the last ``encode_rows`` ran on."""
+        if self._enc is None:
+            raise RuntimeError("NFP.readout_enc follows NFP.encode_rows on the same EncBatch")
+        g_real, pad = self._enc
+        self._enc = None
+        return Fn.NFPInstFn.apply(g_real, pad, eb)
 
     def get_atom_array(self):
         assert self.atoms is not None

@@ -46,6 +46,15 @@ class GraphConvPredictorForPair(nn.Module):
             # per-instance rows copied from it
             eb = atoms_1
             h, h0 = self.graph_conv.encode_rows(eb.pb_enc)
+            readout_enc = getattr(self.graph_conv, "readout_enc", None)
+            if readout_enc is not None:
+                # bmp.nfp.NFP reads out on the ENCODER rows (its readout is as wide as a layer, and under dedup it would save
+                # nothing on the instance rows): only a co-attention reads the atom array, so without one nothing is copied
+                at = None if self.attn is None else PackedAtoms(EncRowsFn.apply(h, eb), eb.pb, None)
+                self.graph_conv.atoms = at
+                g = readout_enc(eb)
+                B = eb.pb.side_mols[1]
+                return g[:B], g[B:], at, at, (0, B)
             rows = EncRowsFn.apply(h, eb)
             rows0 = None if h0 is None else EncRowsFn.apply(h0, eb)
             # (an encoder with a layer aggregator hands over no atom array: models/ggnn_att.py:648-651)

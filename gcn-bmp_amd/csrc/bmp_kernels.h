@@ -161,6 +161,31 @@ extern "C" int bmp_gin_layer_table_bwd(const float* dout, const float* out, cons
                                        int mt_rows, int tile_stride, hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------
+// The NFP layer and readout over a tile table (bmp_nfp_table.hip): bmp_nfp_layer_table_* / bmp_nfp_readout_table_* of
+// include/bmp.h, and what they take from bmp_nfp.hip
+// ---------------------------------------------------------------------------------------------
+extern "C" int bmp_nfp_layer_supported(int d);
+extern "C" int bmp_nfp_readout_tile_supported(int d, int o);
+extern "C" size_t bmp_nfp_readout_bwd_ws_floats(int N, int d, int o);
+extern "C" int bmp_nfp_layer_table_supported(int d);
+extern "C" int bmp_nfp_readout_table_supported(int d, int o);
+extern "C" int bmp_nfp_layer_table_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                                       const float* self_w, const int* deg_class, const float* WTp, const float* B, float* fv,
+                                       float* out, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
+                                       hipStream_t st);
+extern "C" int bmp_nfp_layer_table_bwd(const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
+                                       const float* csrT_val, const float* self_w, const int* deg_class, const float* row_w,
+                                       const float* Wnp, float* dpre, float* dh, const int* mt_row0, const int* mt_nblk, int mt_rows,
+                                       int tile_stride, hipStream_t st);
+extern "C" int bmp_nfp_readout_table_fwd(const float* h, int n_tiles, int d, int o, const float* WoTp, const float* b, const float* row_w,
+                                         const int* row_mol, float* s, float* g, int accumulate, const int* mt_row0,
+                                         const int* mt_nblk, int mt_rows, int tile_stride, hipStream_t st);
+extern "C" int bmp_nfp_readout_table_bwd(const float* dg, const float* h, const float* s, int n_tiles, int d, int o, const float* Wnp,
+                                         const float* row_w, const int* row_mol, float* dh, float* dWT, float* db, float* ws,
+                                         size_t ws_floats, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
+                                         hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------
 // Optional per-kernel-class timing with HIP events (bench.py's roofline leg).  Off by default;
 // the only process-global state in the library.  While a class is armed, every launch of that
 // class is bracketed by two events on the launch stream.

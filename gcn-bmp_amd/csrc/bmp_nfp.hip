@@ -12,9 +12,8 @@
 // The weight gradient of the widths the listed MFMA launch takes (64 <= d <= 128) runs as seven listed problems of
 // bmp_launch_wgrad_fused over the class row lists; the other widths take k_nfp_wgrad below.
 #include <string.h>
-#include "bmp_wtile.h"
+#include "bmp_wtile_nfp.h"
 
-#define NFP_NCLS 7          // degree classes 1..7 (max_degree 6 + 1, nfp.py:26,111); class 0 = none of them
 #define NFP_RB 8            // rows per workgroup of the row-wise kernels (N is a multiple of 128)
 
 static inline size_t nfp_max(size_t a, size_t b) { return a > b ? a : b; }
@@ -44,6 +43,34 @@ extern "C" int bmp_nfp_rows(const int* csrT_ptr, const float* csrT_val, const in
     BMP_REQUIRE(csrT_ptr && row_mol && mol_row0 && mol_nrows && N > 0 && self_w && deg_class);
     hipLaunchKernelGGL(k_nfp_rows, dim3((N + 255) / 256), dim3(256), 0, st, csrT_ptr, csrT_val, row_mol, mol_row0, mol_nrows, N,
                        self_w, deg_class);
+    BMP_LAUNCH_CHECK();
+    return 0;
+}
+
+// The same on the ENCODER layout (bmp/enclayout.py), whose conventions differ: mol_nrows counts real atoms only and row_mol is
+// u >= 0 on a real atom, <= -2 on a tile's pad row and -1 on a dead row.  self_w = 1 exactly where row_mol >= 0; live [N] = 1
+// where row_mol != -1 (real atoms and pad rows: the rows that carry gradient, the layer backward's weight there).
+__global__ __launch_bounds__(256) void k_nfp_rows_enc(const int* __restrict__ ptrT, const float* __restrict__ valT,
+                                                      const int* __restrict__ row_mol, int N, float* __restrict__ self_w,
+                                                      int* __restrict__ deg_class, float* __restrict__ live) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    const int m = row_mol[r];
+    const float sw = m >= 0 ? 1.f : 0.f;
+    float deg = sw;                                   // self loop first, then the column's entries in CSR order
+    for (int e = ptrT[r]; e < ptrT[r + 1]; ++e) deg += valT[e];
+    int k = 0;
+#pragma unroll
+    for (int c = 1; c <= NFP_NCLS; ++c) k = (deg == (float)c) ? c : k;
+    self_w[r] = sw;
+    deg_class[r] = k;
+    live[r] = m != -1 ? 1.f : 0.f;
+}
+
+extern "C" int bmp_nfp_rows_enc(const int* csrT_ptr, const float* csrT_val, const int* row_mol, int N, float* self_w, int* deg_class,
+                                float* live, hipStream_t st) {
+    BMP_REQUIRE(csrT_ptr && row_mol && N > 0 && self_w && deg_class && live);
+    hipLaunchKernelGGL(k_nfp_rows_enc, dim3((N + 255) / 256), dim3(256), 0, st, csrT_ptr, csrT_val, row_mol, N, self_w, deg_class, live);
     BMP_LAUNCH_CHECK();
     return 0;
 }
@@ -435,87 +462,69 @@ extern "C" int bmp_nfp_readout_bwd(const float* dg, const float* h, const float*
     return bmp_launch_colsum(dz, o, N, o, db, 0, cs_ws, st);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The readout of a batch in the encoder layout, per INSTANCE from the sums over the encoder rows (beside bmp_encrows_expand /
+// bmp_encrows_reduce of bmp_enc.hip).  A padded position leaves layer l as sigmoid(B_l) whatever the molecule, so
+//   g_inst[i] = g_real[uid[i]] + padcount[i] * P,   P [o] = sum_l softmax(sigmoid(B_l) . Wo_l^T + bo_l)  (the caller's),
+// padcount[i] = row_w of the instance's pad row (inst_row0[i] + inst_nrows[i] - 1).  The backward sums, per encoded molecule
+// and in the fixed order of uptr / uinst, the gradients of its instances: no atomics, bitwise reproducible.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_nfp_inst_expand(const float* __restrict__ g_real, const float* __restrict__ P, int o,
+                                                         const int* __restrict__ uid, const float* __restrict__ row_w,
+                                                         const int* __restrict__ inst_row0, const int* __restrict__ inst_nrows, int I,
+                                                         float* __restrict__ g_inst) {
+    const int total = I * o;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int i = idx / o, c = idx - i * o;
+        const float pc = row_w[inst_row0[i] + inst_nrows[i] - 1];
+        g_inst[idx] = g_real[(size_t)uid[i] * o + c] + pc * P[c];
+    }
+}
+__global__ __launch_bounds__(256) void k_nfp_inst_reduce(const float* __restrict__ dg_inst, int o, const int* __restrict__ uptr,
+                                                         const int* __restrict__ uinst, int U, float* __restrict__ dg_real) {
+    const int total = U * o;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < total; idx += gridDim.x * 256) {
+        const int u = idx / o, c = idx - u * o;
+        float acc = 0.f;
+        for (int k = uptr[u]; k < uptr[u + 1]; ++k) acc += dg_inst[(size_t)uinst[k] * o + c];
+        dg_real[idx] = acc;
+    }
+}
+static inline int nfp_inst_blocks(int total) {
+    const int b = (total + 255) / 256;
+    return b > 4096 ? 4096 : b;
+}
+extern "C" int bmp_nfp_inst_expand(const float* g_real, const float* P, int o, const int* uid, const float* row_w, const int* inst_row0,
+                                   const int* inst_nrows, int n_inst, float* g_inst, hipStream_t st) {
+    BMP_REQUIRE(g_real && P && o > 0 && uid && row_w && inst_row0 && inst_nrows && n_inst > 0 && g_inst);
+    BMP_REQUIRE((long long)n_inst * o < (1ll << 31));
+    hipLaunchKernelGGL(k_nfp_inst_expand, dim3(nfp_inst_blocks(n_inst * o)), dim3(256), 0, st, g_real, P, o, uid, row_w, inst_row0,
+                       inst_nrows, n_inst, g_inst);
+    BMP_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int bmp_nfp_inst_reduce(const float* dg_inst, int o, const int* uptr, const int* uinst, int n_enc, float* dg_real,
+                                   hipStream_t st) {
+    BMP_REQUIRE(dg_inst && o > 0 && uptr && uinst && n_enc > 0 && dg_real);
+    BMP_REQUIRE((long long)n_enc * o < (1ll << 31));
+    hipLaunchKernelGGL(k_nfp_inst_reduce, dim3(nfp_inst_blocks(n_enc * o)), dim3(256), 0, st, dg_inst, o, uptr, uinst, n_enc, dg_real);
+    BMP_LAUNCH_CHECK();
+    return 0;
+}
+
 // =============================================================================================
 // Fused per-tile forms for d in {64, 128} (exact-f32 MFMA 32x32x2).  One workgroup of 512 threads (8 waves) per 128-row
-// tile; wave w owns the 32-row block w >> 1 of the operand tile and the column half w & 1.
-//
-// Degree-class walk: the tile's rows are ranked by (class 1..7, then class 0; row) -- a fixed order, computed from the
-// classes alone -- and the operand rows (fv forward, dpre backward) are laid into LDS at their ranks.  A 32-row block of
-// the ranked tile then holds a contiguous run of classes; for every class present in the block the wave runs the MFMAs of
-// that class's matrix over the block with the other rows zeroed in the A operand.  Every row belongs to one class, so its
-// accumulators receive its product once plus exact zeros; blocks of class-0 rows (pad rows, dead rows at the tile's end,
-// hubs) run no MFMA at all.  Work = (block, class) pairs present: at most blocks + classes - 1 block passes per tile.
-// Weights are K4-packed per class ([K/4][N][4], as for bmp_ggnn_step_*): a lane's four k values are one 16-byte load.
-// The tile load, the MFMA loop, the wave product, the gather and the launch are the shared ones of bmp_wtile.h.
+// tile; wave w owns the 32-row block w >> 1 of the operand tile and the column half w & 1.  The bodies -- the degree-class
+// walk, the layer both ways, the readout both ways -- are bmp_wtile_nfp.h's, which the tile-table kernels of
+// bmp_nfp_table.hip instantiate too; the tile load, the MFMA loop, the wave product, the gather and the launch are the shared
+// ones of bmp_wtile.h.
 // =============================================================================================
-#define NFP_LDZ 132         // row stride of the readout's z / dz tile (o <= 128)
-
-struct NfpOrder { int scl[WT_R]; int skey[WT_R]; unsigned char inv[WT_R]; unsigned char perm[WT_R]; };
-// rank of every tile row in the order (class 1..7, class 0; row); ends with a workgroup barrier
-__device__ __forceinline__ void nfp_rank_rows(NfpOrder& o, const int* __restrict__ cls, int row0) {
-    const int tid = threadIdx.x;
-    if (tid < WT_R) o.scl[tid] = cls[row0 + tid];
-    __syncthreads();
-    if (tid < WT_R) {
-        const int c = o.scl[tid], key = c ? c : 8;
-        int pos = 0;
-        for (int j = 0; j < WT_R; ++j) {
-            const int cj = o.scl[j], kj = cj ? cj : 8;
-            pos += (kj < key || (kj == key && j < tid)) ? 1 : 0;
-        }
-        o.inv[tid] = (unsigned char)pos;
-        o.perm[pos] = (unsigned char)tid;
-        o.skey[pos] = c;
-    }
-    __syncthreads();
-}
-// the class walk of one wave: acc = ranked block wv.b of `opnd` times the class matrices Wp [7][D x D packed]
-template <int D>
-__device__ __forceinline__ void nfp_class_walk(f32x16 (&acc)[D / 64], const float* opnd, const NfpOrder& o, const float* __restrict__ Wp,
-                                               WtWave wv) {
-    const int c_l = o.skey[wv.b * 32 + (wv.lane & 31)];
-    const WtLane p = wt_wave_open<D>(acc, opnd, D + 4, wv);
-    for (int k = 1; k <= NFP_NCLS; ++k)
-        if (__ballot(c_l == k)) wt_block_mma<D / 64, true>(acc, p.Ar, Wp + (size_t)(k - 1) * D * D + p.boff, D, D, c_l == k);
-}
-
 template <int D>
 __global__ __launch_bounds__(512) void k_nfp_tile_fwd(const float* __restrict__ h, const int* __restrict__ ptr, const int* __restrict__ col,
                                                       const float* __restrict__ val, const float* __restrict__ self_w,
                                                       const int* __restrict__ cls, const float* __restrict__ WTp,
                                                       const float* __restrict__ B, float* __restrict__ fv, float* __restrict__ out) {
-    constexpr int LD = D + 4, NB = D / 64, F = D / 16;
-    extern __shared__ float sm[];
-    float* ht = sm;                        // h tile, tile-row order
-    float* ft = sm + WT_R * LD;            // fv tile, ranked order
-    __shared__ NfpOrder o;
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    wt_load_tile<D>(ht, h, row0, tid);
-    nfp_rank_rows(o, cls, row0);           // (its barriers also publish the h tile)
-    {
-        const int row = tid >> 2, q = tid & 3;
-        f32x4 acc[F];
-        wt_tile_gather<D, true>(acc, ht, row, q, row0, ptr, col, val, self_w[row0 + row]);
-        float* d = ft + o.inv[row] * LD + q * (D / 4);
-        float* gq = fv + (size_t)(row0 + row) * D + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) { *(f32x4*)(d + 4 * f) = acc[f]; *(f32x4*)(gq + 4 * f) = acc[f]; }
-    }
-    __syncthreads();
-    f32x16 acc[NB];
-    nfp_class_walk<D>(acc, ft, o, WTp, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-        const float bc = B[c];
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int row = o.perm[wt_row(wv, reg)];
-            out[(size_t)(row0 + row) * D + c] = bmp_sigmoid(acc[nb][reg] + bc);
-        }
-    }
+    nfp_layer_fwd<D>(h, ptr, col, val, self_w, cls, WTp, B, fv, out);
 }
 
 template <int D>
@@ -524,42 +533,7 @@ __global__ __launch_bounds__(512) void k_nfp_tile_bwd(const float* __restrict__ 
                                                       const float* __restrict__ valT, const float* __restrict__ self_w,
                                                       const int* __restrict__ cls, const float* __restrict__ row_w,
                                                       const float* __restrict__ Wnp, float* __restrict__ dpre, float* __restrict__ dh) {
-    constexpr int LD = D + 4, NB = D / 64, F = D / 16;
-    extern __shared__ float sm[];
-    float* dt = sm;                        // dpre tile, ranked order
-    float* gt = sm + WT_R * LD;            // dfv tile, tile-row order
-    __shared__ NfpOrder o;
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    nfp_rank_rows(o, cls, row0);
-    for (int i = tid; i < WT_R * (D / 4); i += 512) {
-        const int r = i / (D / 4), q4 = i % (D / 4);
-        const size_t g = (size_t)(row0 + r) * D + 4 * q4;
-        const f32x4 ov = *(const f32x4*)(out + g), gv = *(const f32x4*)(dout + g);
-        f32x4 v = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (row_w[row0 + r] != 0.f) v = gv * ov * ((f32x4){1.f, 1.f, 1.f, 1.f} - ov);
-        *(f32x4*)(dpre + g) = v;
-        *(f32x4*)(dt + o.inv[r] * LD + 4 * q4) = v;
-    }
-    __syncthreads();
-    f32x16 acc[NB];
-    nfp_class_walk<D>(acc, dt, o, Wnp, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) gt[o.perm[wt_row(wv, reg)] * LD + c] = acc[nb][reg];
-    }
-    __syncthreads();
-    {
-        const int row = tid >> 2, q = tid & 3;
-        f32x4 a[F];
-        wt_tile_gather<D, true>(a, gt, row, q, row0, ptrT, colT, valT, self_w[row0 + row]);
-        float* gq = dh + (size_t)(row0 + row) * D + q * (D / 4);
-#pragma unroll
-        for (int f = 0; f < F; ++f) *(f32x4*)(gq + 4 * f) = a[f];
-    }
+    nfp_layer_bwd<D>(dout, out, ptrT, colT, valT, self_w, cls, row_w, Wnp, dpre, dh);
 }
 
 extern "C" int bmp_nfp_layer_supported(int d) { return d == 64 || d == 128; }
@@ -568,8 +542,8 @@ extern "C" int bmp_nfp_layer_supported(int d) { return d == 64 || d == 128; }
 extern "C" int bmp_nfp_layer_tile_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
                                       const float* self_w, const int* deg_class, const float* WTp, const float* B, float* fv,
                                       float* out, hipStream_t st) {
-    BMP_REQUIRE(h && n_tiles > 0 && bmp_nfp_layer_supported(d) && csr_ptr && self_w && deg_class && WTp && B && fv && out);
-    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WTp | (uintptr_t)fv) & 15) == 0);
+    if (int rc = nfp_layer_fwd_check(bmp_nfp_layer_supported(d), fv != nullptr, h, n_tiles, csr_ptr, self_w, deg_class, WTp, B, fv, out))
+        return rc;
     WT_LAUNCH(k_nfp_tile_fwd, d, n_tiles, wt_lds_bytes(d), st, h, csr_ptr, csr_col, csr_val, self_w, deg_class, WTp, B, fv, out);
     return 0;
 }
@@ -577,115 +551,45 @@ extern "C" int bmp_nfp_layer_tile_fwd(const float* h, int n_tiles, int d, const 
 extern "C" int bmp_nfp_layer_tile_bwd(const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
                                       const float* csrT_val, const float* self_w, const int* deg_class, const float* row_w,
                                       const float* Wnp, float* dpre, float* dh, hipStream_t st) {
-    BMP_REQUIRE(dout && out && n_tiles > 0 && bmp_nfp_layer_supported(d) && csrT_ptr && self_w && deg_class && row_w && Wnp && dpre && dh);
-    BMP_REQUIRE((((uintptr_t)dout | (uintptr_t)out | (uintptr_t)Wnp | (uintptr_t)dpre | (uintptr_t)dh) & 15) == 0);
+    if (int rc = nfp_layer_bwd_check(bmp_nfp_layer_supported(d), dout, out, n_tiles, csrT_ptr, self_w, deg_class, row_w, Wnp, dpre, dh))
+        return rc;
     WT_LAUNCH(k_nfp_tile_bwd, d, n_tiles, wt_lds_bytes(d), st, dout, out, csrT_ptr, csrT_col, csrT_val, self_w, deg_class, row_w, Wnp, dpre, dh);
     return 0;
 }
 
-// ---- the readout per tile: z = h . W_o + b_o on MFMA (column blocks of 32, o a multiple of 8 up to 128), softmax per row
-// (4 threads per row), the tile's molecules summed in row order by one thread per channel --------------------------------
 template <int D>
 __global__ __launch_bounds__(512) void k_nfp_readout_tile_fwd(const float* __restrict__ h, int o, const float* __restrict__ WoTp,
                                                               const float* __restrict__ bo, const float* __restrict__ row_w,
                                                               const int* __restrict__ row_mol, float* __restrict__ sout,
                                                               float* __restrict__ g, int accumulate) {
-    constexpr int LD = D + 4;
-    extern __shared__ float sm[];
-    float* ht = sm;
-    float* zt = sm + WT_R * LD;            // [128][NFP_LDZ]
-    __shared__ int rmol[WT_R];
-    __shared__ float rw[WT_R];
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int lane = wv.lane;
-    const int row0 = blockIdx.x * WT_R;
-    wt_load_tile<D>(ht, h, row0, tid);
-    if (tid < WT_R) { rmol[tid] = row_mol[row0 + tid]; rw[tid] = row_w[row0 + tid]; }
-    __syncthreads();
-    for (int cb = wv.ch; cb * 32 < o; cb += 2) {
-        const int c = cb * 32 + (lane & 31);
-        const bool valid = c < o;
-        f32x16 acc[1];
-        zero_acc(acc);
-        // (a column past o multiplies column 0's weights; its results are not stored)
-        wt_block_mma<1, false>(acc, ht + (wv.b * 32 + (lane & 31)) * LD + 4 * (lane >> 5),
-                               WoTp + ((size_t)(lane >> 5) * o + (valid ? c : 0)) * 4, o, D);
-        if (valid) {
-            const float bc = bo[c];
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) zt[wt_row(wv, reg) * NFP_LDZ + c] = acc[0][reg] + bc;
-        }
-    }
-    __syncthreads();
-    {
-        const int row = tid >> 2, q = tid & 3;
-        float* z = zt + row * NFP_LDZ;
-        float mx = -3.0e38f;
-        for (int c = q; c < o; c += 4) mx = fmaxf(mx, z[c]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1)); mx = fmaxf(mx, __shfl_xor(mx, 2));
-        float sum = 0.f;
-        for (int c = q; c < o; c += 4) { const float e = bmp_exp(z[c] - mx); z[c] = e; sum += e; }
-        sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2);
-        const float inv = 1.0f / sum;
-        for (int c = q; c < o; c += 4) { const float s = z[c] * inv; z[c] = s; sout[(size_t)(row0 + row) * o + c] = s; }
-    }
-    __syncthreads();
-    if (tid < o) {
-        float acc = 0.f;
-        int cur = -1;
-        for (int r = 0; r <= WT_R; ++r) {
-            const int m = r < WT_R ? rmol[r] : -1;
-            if (m != cur) {
-                if (cur >= 0) { float* p = g + (size_t)cur * o + tid; *p = accumulate ? (*p + acc) : acc; }
-                cur = m; acc = 0.f;
-            }
-            if (m >= 0) acc = fmaf(rw[r], zt[r * NFP_LDZ + tid], acc);
-        }
-    }
+    nfp_readout_fwd<D>(h, o, WoTp, bo, row_w, row_mol, sout, g, accumulate);
 }
 template <int D>
 __global__ __launch_bounds__(512) void k_nfp_readout_tile_bwd(const float* __restrict__ dg, const float* __restrict__ s, int o,
                                                               const float* __restrict__ Wnp, const float* __restrict__ row_w,
                                                               const int* __restrict__ row_mol, float* __restrict__ dz,
                                                               float* __restrict__ dh) {
-    constexpr int NB = D / 64;
-    extern __shared__ float sm[];
-    float* zt = sm;                        // dz tile [128][NFP_LDZ]
-    const int tid = threadIdx.x;
-    const WtWave wv = wt_wave(tid);
-    const int row0 = blockIdx.x * WT_R;
-    {
-        const int row = tid >> 2, q = tid & 3, gr = row0 + row;
-        const int m = row_mol[gr];
-        const float rwv = m >= 0 ? row_w[gr] : 0.f;
-        const bool on = rwv != 0.f;
-        float dot = 0.f;
-        if (on) for (int c = q; c < o; c += 4) dot = fmaf(dg[(size_t)m * o + c], s[(size_t)gr * o + c], dot);
-        dot += __shfl_xor(dot, 1); dot += __shfl_xor(dot, 2);
-        for (int c = q; c < o; c += 4) {
-            const float v = on ? rwv * s[(size_t)gr * o + c] * (dg[(size_t)m * o + c] - dot) : 0.f;
-            zt[row * NFP_LDZ + c] = v;
-            dz[(size_t)gr * o + c] = v;
-        }
+    nfp_readout_bwd<D>(dg, s, o, Wnp, row_w, row_mol, dz, dh);
+}
+
+int nfp_readout_wgrad(const float* h, int N, int d, int o, float* dWT, float* db, float* ws, hipStream_t st) {
+    float* dz = ws;
+    float* slab = dz + (size_t)N * o;
+    float* cs_ws = ws + (bmp_nfp_readout_bwd_ws_floats(N, d, o) - bmp_colsum_ws_floats(N, o));
+    if (o >= 64 && ((uintptr_t)h & 15) == 0) {          // dW_o [d x o] and db on the LDS-staged MFMA weight-gradient GEMM
+        WGArgs gw{h, nullptr, d, 0, dz, o, d, o, N, dWT, o, 0};
+        gw.cs = db;
+        return bmp_launch_wgrad(gw, slab, st);
     }
-    __syncthreads();
-    f32x16 acc[NB];
-    wt_wave_mma<D>(acc, zt, NFP_LDZ, Wnp, o, wv);
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-        const int c = wt_col(wv, NB, nb);
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) dh[(size_t)(row0 + wt_row(wv, reg)) * D + c] = acc[nb][reg];
-    }
+    if (int rc = nfp_launch_wgrad(h, d, dz, o, N, 1, nullptr, nullptr, dWT, slab, st)) return rc;
+    return bmp_launch_colsum(dz, o, N, o, db, 0, cs_ws, st);
 }
 
 extern "C" int bmp_nfp_readout_tile_supported(int d, int o) { return (d == 64 || d == 128) && o >= 8 && o <= 128 && (o & 7) == 0; }
 // WoTp: W_o^T [d x o] K4-packed; row_mol [N].  Every molecule lies in one tile, whose workgroup takes its sum in row order.
 extern "C" int bmp_nfp_readout_tile_fwd(const float* h, int n_tiles, int d, int o, const float* WoTp, const float* b, const float* row_w,
                                         const int* row_mol, float* s, float* g, int accumulate, hipStream_t st) {
-    BMP_REQUIRE(h && n_tiles > 0 && bmp_nfp_readout_tile_supported(d, o) && WoTp && b && row_w && row_mol && s && g);
-    BMP_REQUIRE((((uintptr_t)h | (uintptr_t)WoTp) & 15) == 0);
+    if (int rc = nfp_readout_fwd_check(bmp_nfp_readout_tile_supported(d, o), h, n_tiles, WoTp, b, row_w, row_mol, s, g)) return rc;
     const size_t lds = (size_t)WT_R * (d + 4 + NFP_LDZ) * sizeof(float);
     WT_LAUNCH(k_nfp_readout_tile_fwd, d, n_tiles, lds, st, h, o, WoTp, b, row_w, row_mol, s, g, accumulate);
     return 0;
@@ -694,21 +598,11 @@ extern "C" int bmp_nfp_readout_tile_fwd(const float* h, int n_tiles, int d, int 
 extern "C" int bmp_nfp_readout_tile_bwd(const float* dg, const float* h, const float* s, int n_tiles, int d, int o, const float* Wnp,
                                         const float* row_w, const int* row_mol, float* dh, float* dWT, float* db, float* ws,
                                         size_t ws_floats, hipStream_t st) {
-    BMP_REQUIRE(dg && h && s && n_tiles > 0 && bmp_nfp_readout_tile_supported(d, o) && Wnp && row_w && row_mol && dh && dWT && db && ws);
-    BMP_REQUIRE(((uintptr_t)Wnp & 15) == 0);
+    if (int rc = nfp_readout_bwd_check(bmp_nfp_readout_tile_supported(d, o), dg, h, s, n_tiles, Wnp, row_w, row_mol, dh, dWT, db, ws))
+        return rc;
     const int N = n_tiles * BMP_R;
     BMP_REQUIRE(ws_floats >= bmp_nfp_readout_bwd_ws_floats(N, d, o));
-    float* dz = ws;
-    float* slab = dz + (size_t)N * o;
-    float* cs_ws = ws + (bmp_nfp_readout_bwd_ws_floats(N, d, o) - bmp_colsum_ws_floats(N, o));
     const size_t lds = (size_t)WT_R * NFP_LDZ * sizeof(float);
-    WT_LAUNCH(k_nfp_readout_tile_bwd, d, n_tiles, lds, st, dg, s, o, Wnp, row_w, row_mol, dz, dh);
-    int rc;
-    if (o >= 64 && ((uintptr_t)h & 15) == 0) {          // dW_o [d x o] and db on the LDS-staged MFMA weight-gradient GEMM
-        WGArgs gw{h, nullptr, d, 0, dz, o, d, o, N, dWT, o, 0};
-        gw.cs = db;
-        return bmp_launch_wgrad(gw, slab, st);
-    }
-    if ((rc = nfp_launch_wgrad(h, d, dz, o, N, 1, nullptr, nullptr, dWT, slab, st))) return rc;
-    return bmp_launch_colsum(dz, o, N, o, db, 0, cs_ws, st);
+    WT_LAUNCH(k_nfp_readout_tile_bwd, d, n_tiles, lds, st, dg, s, o, Wnp, row_w, row_mol, ws, dh);
+    return nfp_readout_wgrad(h, N, d, o, dWT, db, ws, st);
 }

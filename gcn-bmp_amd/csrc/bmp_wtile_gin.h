@@ -14,12 +14,7 @@
 // this workgroup's tile and its live rows
 template <bool VAR>
 __device__ __forceinline__ void gin_tile(WgTable tt, int& row0, int& nblk, int& nrows) {
-    wg_tile<VAR>(tt, row0, nblk);
-    nrows = 32 * nblk;
-    if constexpr (VAR) {
-        const int left = tt.mt_rows - row0;
-        nrows = nrows < left ? nrows : (left > 0 ? left : 0);
-    }
+    wg_tile_rows<VAR>(tt, row0, nblk, nrows);
 }
 
 template <int D, bool VAR = false>

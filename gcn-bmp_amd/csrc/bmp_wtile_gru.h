@@ -45,6 +45,16 @@ __device__ __forceinline__ void wg_tile(WgTable tt, int& row0, int& nblk) {
         nblk = WT_R / 32;
     }
 }
+// ... and its live rows, clipped to the arrays (the GIN and NFP kernels)
+template <bool VAR>
+__device__ __forceinline__ void wg_tile_rows(WgTable tt, int& row0, int& nblk, int& nrows) {
+    wg_tile<VAR>(tt, row0, nblk);
+    nrows = 32 * nblk;
+    if constexpr (VAR) {
+        const int left = tt.mt_rows - row0;
+        nrows = nrows < left ? nrows : (left > 0 ? left : 0);
+    }
+}
 // the end of the rows a fixed-stride table's tile clears behind its live rows (none: row0 + nrows), clipped to the arrays
 __device__ __forceinline__ int wg_dead_end(WgTable tt, int row0, int nrows) {
     const int e = row0 + (tt.tile_stride > nrows ? tt.tile_stride : nrows);

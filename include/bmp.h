@@ -466,6 +466,47 @@ int bmp_nfp_readout_tile_fwd(const float* h, int n_tiles, int d, int o, const fl
 int bmp_nfp_readout_tile_bwd(const float* dg, const float* h, const float* s, int n_tiles, int d, int o, const float* Wnp,
                              const float* row_w, const int* row_mol, float* dh, float* dWT, float* db, float* ws, size_t ws_floats,
                              bmp_stream_t stream);
+/* The same layer and readout over a TILE TABLE (csrc/bmp_nfp_table.hip), for batches in the encoder layout and the fixed-shape
+ * batch, under the contract of bmp_gin_layer_table_*: n_tiles table entries, entry t = rows [mt_row0[t], mt_row0[t] + 32
+ * mt_nblk[t]) with 1..4 live 32-row blocks, one workgroup each; no molecule straddles an entry; mt_rows = the rows of the arrays.
+ * No row behind an entry's live rows is read -- not h, deg_class, self_w, row_w or row_mol: those rows rank as class 0 -- or
+ * written, a CSR entry whose source row lies outside the entry's live rows is skipped, and the waves of a block without live rows
+ * skip their products.  tile_stride: 0 (dense rows) or the table's fixed stride (a multiple of 32, >= 128): the rows [mt_row0[t] +
+ * 32 mt_nblk[t], mt_row0[t] + tile_stride) are then written as ZEROS in every row array the call writes (layer fwd: fv, out; bwd:
+ * dpre, dh; readout fwd: s; bwd: dh and the dz workspace, the first mt_rows x o floats of ws); dB, db and the weight gradients
+ * sum over all mt_rows rows.  Layer fwd: fv may be NULL (forward-only evaluation): it is not stored.  Layer bwd: row_w is the
+ * weight whose zeros leave with dpre == 0 -- the batch's row_w, or on the encoder layout, whose pad rows have row_w == 0 and
+ * still carry gradient, the liveness weight of bmp_nfp_rows_enc.  Readout bwd: ws holds bmp_nfp_readout_bwd_ws_floats(mt_rows,
+ * d, o) floats.  Everything else is as for the _tile_ entries, and a table of whole tiles at 128 t gives their results bit for
+ * bit.  Widths: bmp_nfp_layer_table_supported(d) (64 or 128), bmp_nfp_readout_table_supported(d, o) (as the _tile_ readout). */
+int bmp_nfp_layer_table_supported(int d);
+int bmp_nfp_readout_table_supported(int d, int o);
+int bmp_nfp_layer_table_fwd(const float* h, int n_tiles, int d, const int* csr_ptr, const int* csr_col, const float* csr_val,
+                            const float* self_w, const int* deg_class, const float* WTp, const float* B, float* fv, float* out,
+                            const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, bmp_stream_t stream);
+int bmp_nfp_layer_table_bwd(const float* dout, const float* out, int n_tiles, int d, const int* csrT_ptr, const int* csrT_col,
+                            const float* csrT_val, const float* self_w, const int* deg_class, const float* row_w, const float* Wnp,
+                            float* dpre, float* dh, const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride,
+                            bmp_stream_t stream);
+int bmp_nfp_readout_table_fwd(const float* h, int n_tiles, int d, int o, const float* WoTp, const float* b, const float* row_w,
+                              const int* row_mol, float* s, float* g, int accumulate, const int* mt_row0, const int* mt_nblk,
+                              int mt_rows, int tile_stride, bmp_stream_t stream);
+int bmp_nfp_readout_table_bwd(const float* dg, const float* h, const float* s, int n_tiles, int d, int o, const float* Wnp,
+                              const float* row_w, const int* row_mol, float* dh, float* dWT, float* db, float* ws, size_t ws_floats,
+                              const int* mt_row0, const int* mt_nblk, int mt_rows, int tile_stride, bmp_stream_t stream);
+/* The encoder layout (bmp/enclayout.py): row_mol is u >= 0 on a real atom, <= -2 on a tile's pad row, -1 on a dead row.
+ * bmp_nfp_rows_enc: self_w = 1 exactly where row_mol >= 0, deg_class from self_w + the transposed-CSR values in entry order,
+ * live [N] = 1 where row_mol != -1.  The readout there sums over the REAL atoms of every encoded molecule (g_real [U x o]); an
+ * instance adds its padded positions, which leave layer l as sigmoid(B_l) whatever the molecule:
+ *   bmp_nfp_inst_expand: g_inst[i] = g_real[uid[i]] + row_w[inst_row0[i] + inst_nrows[i] - 1] * P,  P [o] the caller's sum over
+ *                        the layers of softmax(sigmoid(B_l) . Wo_l^T + bo_l); row_w / inst_row0 / inst_nrows: the per-instance batch's
+ *   bmp_nfp_inst_reduce: dg_real[u] = sum of dg_inst over the instances uinst[uptr[u] : uptr[u + 1]], in that order (no atomics). */
+int bmp_nfp_rows_enc(const int* csrT_ptr, const float* csrT_val, const int* row_mol, int N, float* self_w, int* deg_class,
+                     float* live, bmp_stream_t stream);
+int bmp_nfp_inst_expand(const float* g_real, const float* P, int o, const int* uid, const float* row_w, const int* inst_row0,
+                        const int* inst_nrows, int n_inst, float* g_inst, bmp_stream_t stream);
+int bmp_nfp_inst_reduce(const float* dg_inst, int o, const int* uptr, const int* uinst, int n_enc, float* dg_real,
+                        bmp_stream_t stream);
 
 /* Gated-sum readout -- GGNN.readout models/ggnn.py:333-341 and GGNNReadout.__call__
  * models/readout/ggnn_readout.py:42-57.  g[mol] = sum_rows w * sigmoid(i(.)) * act_j(j(.)).
