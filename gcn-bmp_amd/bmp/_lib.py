@@ -53,6 +53,12 @@ SIGNATURES = {
     "bmp_relgcn_layer_bwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "bmp_relgcn_layer_wgrad_ws_floats": (_Z, [_I, _I]),
     "bmp_relgcn_layer_wgrad": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    "bmp_relgcn_rect_supported": (_I, [_I, _I]),
+    "bmp_relgcn_rect_lists_used": (_I, [_I, _I, _I]),
+    "bmp_relgcn_rect_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P]),
+    "bmp_relgcn_rect_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "bmp_relgcn_rect_wgrad_ws_floats": (_Z, [_I, _I, _I]),
+    "bmp_relgcn_rect_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _Z, _P]),
     "bmp_nfp_rows": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P]),
     "bmp_nfp_deg_rows_ws_ints": (_Z, [_I]),
     "bmp_nfp_deg_rows": (_I, [_P, _I, _P, _P, _P, _P]),

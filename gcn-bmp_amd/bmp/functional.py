@@ -943,6 +943,158 @@ class PRelLayerFn(Function):
         return dx, None, None, None, None, None, None, None
 
 
+# ---- the same layer for d_in != d_out (csrc/bmp_relgcn_rect.hip) ----
+REL_PATHS = {"fused": 0, "composed": 0}          # forward calls per form of a RelGCN layer (square or rectangular kernel: fused)
+REL_RECT_PAIRS = tuple((di, do) for di in (16, 32, 64, 128) for do in (32, 64, 128) if di != do)
+# The (d_in, d_out) pairs whose rectangular kernels beat the unfused operators by the project's rule -- by more than the two
+# forms' p90 - median spreads together in at least three of four runs on the 1024-pair DDI-shaped batch, per instance, in the
+# encoder layout and in the encoder layout with dedup, for one layer forward + backward + weight gradients
+# (tools/relgcn_rect_probe.py, profiles/relgcn_rect_probe.json).  The rule is necessary, not sufficient; a pair that
+# was not measured is False: it keeps the unfused operators, its kernels reachable by setting the entry.  An entry is read when a
+# layer is called eagerly and when a layout plan is built (FlatAdam): a plan keeps the forms it was built with.  Measured (fused against
+# unfused, medians of the first of four runs per instance / encoder layout / with dedup): 128 -> 64: 240 against 394 us, 239 against 392 us, 182 against 282 us;
+# 16 -> 64: 205 against 291 us, 205 against 291 us, 152 against 230 us; 64 -> 32: 207 against 315 us, 207 against 314 us, 178
+# against 253 us: all three pass in 4 of 4 runs in every layout.  16 -> 128 passes too (3, 4 and 4 of 4 runs: 279 against 318 us,
+# 271 against 318 us, 141 against 226 us) and stays False all the same: as the first layer of the default stack its weight gradients
+# -- the all-rows launches at K = 16, behind the LAST kernel of the backward chain -- cannot overlap the chain as the unfused
+# operator's do, and the planned 1024-pair training step of the default RelGCN + MLP model measures 897 us with it on against
+# 851 us with every pair off and 820 us with 128 -> 64 alone.  Set the entry for a recorded 32-pair step, which
+# it helps: 0.40 ms per replay against 0.50 ms with 128 -> 64 alone and 0.60 ms with every pair off.
+REL_RECT_DEFAULT = {p: p in ((128, 64), (16, 64), (64, 32)) for p in REL_RECT_PAIRS}
+
+
+def rel_rect_supported(d_in: int, d_out: int) -> bool:
+    return bool(_lib.lib().bmp_relgcn_rect_supported(int(d_in), int(d_out)))
+
+
+def rel_form(d_in: int, d_out: int):
+    """The kernel form of a RelGCN layer of these widths: "square" (RelLayerFn), "rect" (RelRectLayerFn: supported and switched
+    on in REL_RECT_DEFAULT) or None (the unfused operators)."""
+    if rel_layer_supported(d_in, d_out):
+        return "square"
+    if REL_RECT_DEFAULT.get((int(d_in), int(d_out)), False) and rel_rect_supported(d_in, d_out):
+        return "rect"
+    return None
+
+
+def rel_rect_pack_bwd(WT: torch.Tensor, WsT: torch.Tensor):
+    """(Wnat_p, Ws_p) of the rectangular backward kernel from WT [4 d_in x d_out] and WsT [d_in x d_out]: WT^T per bond type and
+    WsT^T, every block max(d_in, 32) columns wide (at d_in = 16 the 16 columns behind a block's own are zeros: an MFMA block is
+    32 columns), K4-packed."""
+    d_in, d_out = WsT.shape
+    dip = max(d_in, 32)
+    Wn = WT.detach().reshape(4, d_in, d_out)
+    Ws = WsT.detach()
+    if dip != d_in:
+        Wn = torch.cat((Wn, Wn.new_zeros(4, dip - d_in, d_out)), dim=1)
+        Ws = torch.cat((Ws, Ws.new_zeros(dip - d_in, d_out)), dim=0)
+    return pack_k4(Wn.permute(2, 0, 1).reshape(d_out, 4 * dip)), pack_k4(Ws.t())
+
+
+def rel_rect_lists(pb, N: int, d_in: int, d_out: int):
+    """``step_lists`` for the rectangular layer: (idx, cnt, 1) only where bmp_relgcn_rect_wgrad reads gda through the lists."""
+    tri, trc = type_rows(pb)
+    if tri is None or not _lib.lib().bmp_relgcn_rect_lists_used(int(N), int(d_in), int(d_out)):
+        return None, None, 0
+    return tri, trc, 1
+
+
+def _rel_rect_fwd(x, pb, WTp, bE, WsTp, bs, act, state=None, bufs=None):
+    L = _lib.lib()
+    N, d_in = x.shape
+    d_out = bE.shape[1]
+    out, wdeg = bufs if bufs is not None else rel_buffers(N, d_out, x.device)
+    if wdeg is not None:
+        type_rows(pb)                   # (once per batch, on the chain's stream: the backward's weight-gradient launches walk them)
+    mt0, mtn = _rel_mt(pb)
+    for t0, nt, st in _fwd_parts(state, pb, (x, out, wdeg)):
+        check(L.bmp_relgcn_rect_fwd(ptr(x), t0, nt, d_in, d_out, ptr(pb.csr_ptr), ptr(pb.csr_col), ptr(pb.csr_val), ptr(WTp), ptr(bE),
+                                    ptr(WsTp), ptr(bs), act, ptr(out), ptr(wdeg), ptr(mt0), ptr(mtn), pb.n_rows, st),
+              "bmp_relgcn_rect_fwd")
+    return out, wdeg
+
+
+def _rel_rect_bwd(dout, out, x, wdeg, pb, Wnat_p, Ws_p, act, o1, dbE, cs, accumulate, state=None):
+    L = _lib.lib()
+    N, d_in = x.shape
+    d_out = dout.shape[1]
+    dx = torch.empty(N, d_in, dtype=torch.float32, device=x.device)
+    gda = torch.empty(N, 5 * d_out, dtype=torch.float32, device=x.device)
+    tri, trc, skip = rel_rect_lists(pb, N, d_in, d_out)
+    mt0, mtn = _rel_mt(pb)
+    check(L.bmp_relgcn_rect_bwd(ptr(dout), ptr(out), act, pb.n_mtiles, d_in, d_out, ptr(pb.csrT_ptr), ptr(pb.csrT_col), ptr(pb.csrT_val),
+                                ptr(Wnat_p), ptr(Ws_p), ptr(dx), ptr(gda), ptr(mt0), ptr(mtn), pb.n_rows, skip, stream()),
+          "bmp_relgcn_rect_bwd")
+
+    def wgrad(st, ws_of):
+        nws = L.bmp_relgcn_rect_wgrad_ws_floats(N, d_in, d_out)
+        ws = ws_of(nws, x.device)
+        check(L.bmp_relgcn_rect_wgrad(ptr(x), ptr(wdeg), ptr(gda), N, d_in, d_out, ptr(o1), ptr(dbE), ptr(cs), int(accumulate), ptr(tri),
+                                      ptr(trc), ptr(ws), nws, st), "bmp_relgcn_rect_wgrad")
+
+    _on_side(state, (x, wdeg, gda), wgrad)
+    return dx
+
+
+class RelRectLayerFn(Function):
+    """RelLayerFn for d_in != d_out (rel_rect_supported): ONE kernel per tile and direction.  Weight layouts as MsgFn:
+    WT [4 d_in x d_out], bE [4 x d_out], WsT [d_in x d_out], bs [d_out]."""
+
+    @staticmethod
+    def forward(ctx, x, WT, bE, WsT, bs, pb, act):
+        require_rows(x, "relgcn layer: x")
+        _check_pb(pb, x)
+        d_in, d_out = x.shape[1], WT.shape[1]
+        if tuple(WT.shape) != (4 * d_in, d_out) or tuple(WsT.shape) != (d_in, d_out) or tuple(bE.shape) != (4, d_out):
+            raise ValueError("relgcn layer: weight shapes do not match x")
+        if not rel_rect_supported(d_in, d_out):
+            raise ValueError(f"relgcn layer: no rectangular kernel for {d_in} -> {d_out}")
+        infer = not any(ctx.needs_input_grad)        # under no_grad nothing is kept for a backward
+        out, wdeg = _rel_rect_fwd(x, pb, pack_k4(WT), bE.contiguous(), pack_k4(WsT), bs.contiguous(), act,
+                                  bufs=rel_buffers(x.shape[0], d_out, x.device, infer))
+        if not infer:
+            ctx.save_for_backward(x, WT, WsT, out, wdeg)
+        ctx.pb, ctx.act = pb, act
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, WT, WsT, out, wdeg = ctx.saved_tensors
+        d_in, d_out = WsT.shape
+        f = lambda *s_: torch.empty(*s_, dtype=torch.float32, device=x.device)
+        o1, dbE, cs = f(d_in, 5 * d_out), f(4, d_out), f(5 * d_out)
+        Wnat_p, Ws_p = rel_rect_pack_bwd(WT, WsT)
+        dx = _rel_rect_bwd(dout.contiguous(), out, x, wdeg, ctx.pb, Wnat_p, Ws_p, ctx.act, o1, dbE, cs, 0)
+        dWT = o1[:, :4 * d_out].reshape(d_in, 4, d_out).permute(1, 0, 2).reshape(4 * d_in, d_out)      # [k][e*d_out+c] -> [e*d_in+k][c]
+        return dx, dWT, dbE, o1[:, 4 * d_out:], cs[4 * d_out:], None, None
+
+
+class PRelRectLayerFn(Function):
+    """RelRectLayerFn on prepared weights (bmp/plan.py).  W: WTp, bE, WsTp, bs, Wnat_p, Ws_p (rel_rect_pack_bwd);
+    G: o1 [d_in x 5 d_out], dbE [4 x d_out], cs [5 d_out]."""
+
+    @staticmethod
+    def forward(ctx, x, pb, W, G, state, gkey, act, bufs=None):
+        require_rows(x, "relgcn layer: x")
+        _check_pb(pb, x)
+        if bufs is None:                # (a stack with an unfused layer allocates layer by layer) under no_grad no wdeg is kept
+            bufs = rel_buffers(x.shape[0], W["bE"].shape[1], x.device, not any(ctx.needs_input_grad))
+        out, wdeg = _rel_rect_fwd(x, pb, W["WTp"], W["bE"], W["WsTp"], W["bs"], act, state, bufs)
+        ctx.save_for_backward(x, out, wdeg)
+        ctx.pb, ctx.W, ctx.G, ctx.state, ctx.gkey, ctx.act = pb, W, G, state, gkey, act
+        _register(state, gkey)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, out, wdeg = ctx.saved_tensors
+        W, G = ctx.W, ctx.G
+        first = _first_write(ctx.state, ctx.gkey)
+        dx = _rel_rect_bwd(dout.contiguous(), out, x, wdeg, ctx.pb, W["Wnat_p"], W["Ws_p"], ctx.act, G["o1"], G["dbE"], G["cs"],
+                           0 if first else 1, ctx.state)
+        return dx, None, None, None, None, None, None, None
+
+
 # ---------------------------------------------------------------------------------------------------------
 # Neural-fingerprint encoder (models/models/nfp.py; csrc/bmp_nfp.hip).  ``nd`` is the batch's derived NFP data
 # (bmp.nfp.nfp_derived): self_w, deg_class, deg_rows, deg_cnt, bwd_w.  On the tile-table seam further down (_table_ok, _table_args).

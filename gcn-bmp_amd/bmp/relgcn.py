@@ -60,8 +60,12 @@ class RelGCNUpdate(nn.Module):
         """hs + sum_e adj_e (W_e h + b_e) (relgcn_update.py:24-44); ``act`` lets the caller fuse the
         tanh of models/relgcn.py:71 into the same kernel."""
         WT, bE = message_kernel_weights(self.graph_linear_edge)
-        if h.is_cuda and not pb.oversized and Fn.rel_layer_supported(self.in_channels, self.out_channels):
+        form = Fn.rel_form(self.in_channels, self.out_channels) if h.is_cuda and not pb.oversized else None
+        Fn.REL_PATHS["fused" if form else "composed"] += 1
+        if form == "square":
             return Fn.RelLayerFn.apply(h, WT, bE, self.graph_linear_self.W.t(), self.graph_linear_self.b, pb, Fn.ACT[act])
+        if form == "rect":          # d_in != d_out: the default stack [16, 128, 64] (models/relgcn.py:37)
+            return Fn.RelRectLayerFn.apply(h, WT, bE, self.graph_linear_self.W.t(), self.graph_linear_self.b, pb, Fn.ACT[act])
         return Fn.MsgFn.apply(h, WT, bE, self.graph_linear_self.W.t(), self.graph_linear_self.b, pb, Fn.ACT[act])
 
 
@@ -149,10 +153,19 @@ class RelGCN(nn.Module):
         out["ro.WT"] = torch.cat((ro.i_layer.W.t(), ro.j_layer.W.t()), dim=1).contiguous()
         return out
 
-    def _fused(self, l) -> bool:
-        """Layer l runs as the fused tile kernel (d_in == d_out in {64, 128}); otherwise bmp_msg_fwd/bwd."""
+    def _fused(self, l):
+        """The fused tile kernel layer l runs as: "square" (d_in == d_out in {64, 128}), "rect" (d_in != d_out, Fn.rel_form) or
+        None: bmp_msg_fwd/bwd."""
         conv = self.rgcn_convs[l]
-        return Fn.rel_layer_supported(conv.in_channels, conv.out_channels)
+        return Fn.rel_form(conv.in_channels, conv.out_channels)
+
+    def _plan_form(self, P, l):
+        """The form layer l has in the plan whose prepared arrays are ``P``: what ``_fused(l)`` answered when that plan was built
+        (its K4 packs exist or not), whatever ``Fn.REL_RECT_DEFAULT`` holds now."""
+        if f"c{l}.WTp" not in P:
+            return None
+        conv = self.rgcn_convs[l]
+        return "rect" if conv.in_channels != conv.out_channels else "square"
 
     def prepared_layouts(self):
         p = self.primary_layouts()
@@ -161,7 +174,10 @@ class RelGCN(nn.Module):
             if self._fused(l):
                 WT, WsT = p[f"c{l}.WT"], p[f"c{l}.WsT"]
                 out[f"c{l}.WTp"], out[f"c{l}.WsTp"] = Fn.pack_k4(WT), Fn.pack_k4(WsT)
-                out[f"c{l}.Wnat_p"], out[f"c{l}.Ws_p"] = Fn.pack_k4(WT.t()), Fn.pack_k4(WsT.t())
+                if self._fused(l) == "rect":         # (blocks padded to 32 columns at d_in = 16)
+                    out[f"c{l}.Wnat_p"], out[f"c{l}.Ws_p"] = Fn.rel_rect_pack_bwd(WT, WsT)
+                else:
+                    out[f"c{l}.Wnat_p"], out[f"c{l}.Ws_p"] = Fn.pack_k4(WT.t()), Fn.pack_k4(WsT.t())
             else:
                 out[f"c{l}.Wnat"] = p[f"c{l}.WT"].t().contiguous()
                 out[f"c{l}.Ws"] = p[f"c{l}.WsT"].t().contiguous()
@@ -175,7 +191,7 @@ class RelGCN(nn.Module):
         for l, conv in enumerate(self.rgcn_convs):
             di, do = conv.in_channels, conv.out_channels
             if self._fused(l):
-                spec.update({f"c{l}.o1": (di, 5 * di), f"c{l}.dbE": (4, do), f"c{l}.cs": (5 * di,)})
+                spec.update({f"c{l}.o1": (di, 5 * do), f"c{l}.dbE": (4, do), f"c{l}.cs": (5 * do,)})
             else:
                 spec.update({f"c{l}.dWT": (4 * di, do), f"c{l}.dbE": (4, do), f"c{l}.dWsT": (di, do), f"c{l}.dbs": (do,)})
         spec["ro.dWT"] = (self.hidden_dim, 2 * self.out_dim)
@@ -185,12 +201,12 @@ class RelGCN(nn.Module):
         out = {"embed.W": [gk["embed.dW"]], "ro.WT": [gk["ro.dWT"]]}
         for l, conv in enumerate(self.rgcn_convs):
             if self._fused(l):
-                d = conv.in_channels
+                di, do = conv.in_channels, conv.out_channels
                 o1, cs = gk[f"c{l}.o1"], gk[f"c{l}.cs"]
-                out[f"c{l}.WT"] = [o1[:, :4 * d].reshape(d, 4, d).permute(1, 0, 2).reshape(4 * d, d)]
-                out[f"c{l}.WsT"] = [o1[:, 4 * d:]]
+                out[f"c{l}.WT"] = [o1[:, :4 * do].reshape(di, 4, do).permute(1, 0, 2).reshape(4 * di, do)]
+                out[f"c{l}.WsT"] = [o1[:, 4 * do:]]
                 out[f"c{l}.bE"] = [gk[f"c{l}.dbE"]]
-                out[f"c{l}.bs"] = [cs[4 * d:]]
+                out[f"c{l}.bs"] = [cs[4 * do:]]
             else:
                 for a, b in (("WT", "dWT"), ("bE", "dbE"), ("WsT", "dWsT"), ("bs", "dbs")):
                     out[f"c{l}.{a}"] = [gk[f"c{l}.{b}"]]
@@ -232,21 +248,25 @@ class RelGCN(nn.Module):
         pb.check_atom_ids(P["embed.W"].shape[0])
         x = Fn.PEmbedFn.apply(tape, P["embed.W"], pb.atom_id, G["embed.dW"], state)
         pbs = rescale_adj(pb) if self.scale_adj else pb
-        all_fused = all(self._fused(l) for l in range(len(self.rgcn_convs)))
+        forms = [self._plan_form(P, l) for l in range(len(self.rgcn_convs))]      # frozen when the plan was built
+        all_fused = all(forms)
         bufs = None
         if all_fused:         # every layer's outputs first, then the chains of tiles opened once (Fn.fork_parts)
             infer = not torch.is_grad_enabled()      # predict under no-backprop: nothing is kept for a backward
             bufs = [Fn.rel_buffers(x.shape[0], self.rgcn_convs[l].out_channels, x.device, infer) for l in range(len(self.rgcn_convs))]
             Fn.fork_parts(state, pb)
         for l in range(len(self.rgcn_convs)):
-            if self._fused(l):
+            if forms[l]:
                 W = {k: P[f"c{l}.{k}"] for k in ("WTp", "bE", "WsTp", "bs", "Wnat_p", "Ws_p")}
                 Gl = {k: G[f"c{l}.{k}"] for k in ("o1", "dbE", "cs")}
-                x = Fn.PRelLayerFn.apply(x, pbs, W, Gl, state, f"c{l}", Fn.ACT["tanh"], None if bufs is None else bufs[l])
+                layer = Fn.PRelRectLayerFn if forms[l] == "rect" else Fn.PRelLayerFn
+                Fn.REL_PATHS["fused"] += 1
+                x = layer.apply(x, pbs, W, Gl, state, f"c{l}", Fn.ACT["tanh"], None if bufs is None else bufs[l])
                 continue
             W = {k: P[f"c{l}.{k}"] for k in ("WT", "bE", "WsT", "bs", "Wnat", "Ws")}
             Gl = {k: G[f"c{l}.{k}"] for k in ("dWT", "dbE", "dWsT", "dbs")}
             Fn._join_parts(state)             # an unfused layer reads whole arrays
+            Fn.REL_PATHS["composed"] += 1
             x = Fn.PMsgFn.apply(x, pbs, W, Gl, state, f"c{l}", Fn.ACT["tanh"])
         Fn._join_parts(state)                 # fused layers ran as two chains of tiles
         return x, None

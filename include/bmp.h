@@ -190,6 +190,34 @@ int bmp_relgcn_layer_wgrad(const float* h, const float* wdeg, const float* gda, 
                            float* cs, int accumulate, const int* type_rows, const int* type_cnt, float* ws, size_t ws_floats,
                            bmp_stream_t stream);          /* type_rows / type_cnt: as bmp_ggnn_step_wgrad */
 
+/* The same layer for d_in != d_out (csrc/bmp_relgcn_rect.hip): the default stack of models/relgcn.py:37, ch_list = [16, 128, 64],
+ * which is the only RelGCN the reference's scripts build (smiles_based_ddi.py:275, RelGCN(out_channels=fp_out_dim,
+ * scale_adj=True)), changes width in every layer.  Gather first, then multiply (models/update/relgcn_update.py:24-44 sums the
+ * same terms in the order linear, then adjacency).  bmp_relgcn_rect_supported: d_in in {16, 32, 64, 128}, d_out in {32, 64, 128},
+ * d_in != d_out; everything else, d_out = 16 included, uses bmp_msg_fwd/bwd.
+ * fwd: WT [4 d_in x d_out] and WsT [d_in x d_out] K4-packed; saves wdeg [N x 4] unless it is NULL.
+ * bwd: Wnat [d_out x 4 dip] = WT^T per type and Ws [d_out x dip] = WsT^T, K4-packed, dip = max(d_in, 32): at d_in = 16 every
+ * block's 16 columns are followed by 16 zero columns.  Writes dh [N x d_in] and gda [N x 5 d_out] = [G_0..G_3 | dpre].
+ * A tile table (mt_row0 / mt_nblk both or neither, mt_rows > 0) has dense rows; no access goes to a row >= mt_rows.
+ * wgrad: o1 [d_in x 5 d_out] = h^T.gda (cols [0, 4 d_out): dWT as [k][e * d_out + c]; cols [4 d_out, 5 d_out): dWsT),
+ * dbE [4 x d_out] = wdeg^T.dpre, cs [5 d_out] = column sums of gda (cs[4 d_out:] = dbs).  With d_in >= 64 and d_out >= 64 it is
+ * one launch of the fused weight-gradient GEMM (N a multiple of 32), which reads gda's per-type blocks through type_rows when
+ * bmp_relgcn_rect_lists_used(N, d_in, d_out); for every other pair it is the all-rows launches (N a multiple of 8), which read
+ * every row of gda: bmp_relgcn_rect_lists_used is 0 and bmp_relgcn_rect_bwd refuses skip_zero_g != 0 (it returns a non-zero
+ * code and launches nothing), so no block that is left unwritten is ever read. */
+int bmp_relgcn_rect_supported(int d_in, int d_out);
+int bmp_relgcn_rect_lists_used(int N, int d_in, int d_out);
+int bmp_relgcn_rect_fwd(const float* h, int tile0, int n_tiles, int d_in, int d_out, const int* csr_ptr, const int* csr_col,
+                        const float* csr_val, const float* WT, const float* bE, const float* WsT, const float* bs, int act, float* out,
+                        float* wdeg, const int* mt_row0, const int* mt_nblk, int mt_rows, bmp_stream_t stream);
+int bmp_relgcn_rect_bwd(const float* dout, const float* out, int act, int n_tiles, int d_in, int d_out, const int* csrT_ptr,
+                        const int* csrT_col, const float* csrT_val, const float* Wnat, const float* Ws, float* dh, float* gda,
+                        const int* mt_row0, const int* mt_nblk, int mt_rows, int skip_zero_g, bmp_stream_t stream);
+size_t bmp_relgcn_rect_wgrad_ws_floats(int N, int d_in, int d_out);
+int bmp_relgcn_rect_wgrad(const float* h, const float* wdeg, const float* gda, int N, int d_in, int d_out, float* o1, float* dbE,
+                          float* cs, int accumulate, const int* type_rows, const int* type_cnt, float* ws, size_t ws_floats,
+                          bmp_stream_t stream);
+
 /* ---- Graph isomorphism network (GIN) layer -- models/gin.py:89-128 (csrc/bmp_gin.hip) ----
  * s = h + sum over the forward CSR of val * h[csr_col >> 2] (the adjacency summed over the bond types, every entry with its
  * value); t = relu(s . W1^T + b1); out = relu(keep * (t . W2^T + b2)).  keep [N x d]: the dropout mask between the second linear
