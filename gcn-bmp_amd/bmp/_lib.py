@@ -166,6 +166,7 @@ SIGNATURES = {
     "bmp_adam_step": (_I, [_P, _P, _P, _P, _I, _F, _P, _F, _F, _F, _F, _F, _P]),
     "bmp_grad_sumsq_partials": (_I, [_P, _P, _P, _I, _F, _F, _F, _P, _I, _P]),
     "bmp_adam_step_hooked": (_I, [_P, _P, _P, _P, _I, _F, _P, _F, _F, _F, _F, _F, _F, _F, _F, _P, _I, _P, _P, _P]),
+    "bmp_eval_append": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
     "bmp_coattn_zcols": (_I, [_I, _I]),
     "bmp_coattn_nie_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _I] + [_P] * 7 + [_I, _P, _I, _I, _I, _I, _I, _I] + [_P] * 17 + [_P, _Z, _P]),
     "bmp_coattn_big_ws_floats": (_Z, [_I] * 5),

@@ -454,3 +454,92 @@ class GraphedTrainStep:
                 o._gscale = 1.0
         o.t = t_before
         return ga, gb, loss, grad, pb, t
+
+
+class GraphedPredict:
+    """The forward-only twin of ``GraphedTrainStep``: the evaluation pass on a ``bmp.packed.StaticPairBatch`` -- the batch's
+    ``reset_derived`` + ``emit``, ``opt.functional_predict``, the loss against the batch's labels when a loss function is given,
+    and the append of logits, labels, loss and (when asked) the two molecule vectors to a ``bmp.trainer.ScoreSink`` -- recorded
+    ONCE as a HIP graph, under ``torch.no_grad()`` with the model in ``eval()``, and replayed for every batch loaded into that
+    object.  What the evaluators run over the train and the validation set every epoch (training/extensions/
+    batch_evaluator.py:49-100) and the evaluation scripts' ``predict`` (eval_coattention.py:103-124) then cost one submission
+    per batch and no host round trip: the sink's append reads its write position from device memory, so every replay lands
+    behind the one before, and the set comes to the host in ``sink.finish()``'s one copy.
+
+    ``functional_predict`` calls ``plan.prepare(opt.flat)`` and that launch is part of the recording: a replay after an
+    optimizer step sees the new parameters.  The sink's buffers exist, sized, before recording -- their addresses are in the
+    graph -- so ``set_sink`` with another sink drops the recordings.  One graph per (batch object, loss function,
+    representations); the key is the batch's arrays as in ``GraphedTrainStep``.  The warm-up runs on a side stream and its
+    appends are taken back (the sink's three words are restored).  The forward-only path creates nothing per stream: the zero
+    word of the fused MLP + loss head (bmp.mlp._ticket) belongs to ``forward_loss``, which an evaluation does not run.
+
+    ``__call__(static)`` returns the logits tensor of the recording, valid until the next replay; with ``sink=None`` it is a
+    plain replayed ``predict``.  With ``opt.world > 1`` nothing changes: the forward has no collective, every rank evaluates its
+    own share.  The coarse co-attention family (bmp.coarse) reads ``pb.mol_nrows_host`` on the host and sizes tensors by it
+    -- sizes read while recording would be frozen into the graph -- so such a model takes the same body eagerly."""
+
+    capacity_hint = None        # (rows, batches) the caller expects to need at most: bmp.trainer sizes a new sink by it
+
+    def __init__(self, model, opt: "FlatAdam", sink=None, warmup: int = 2):
+        if not opt.flat.is_cuda:
+            raise ValueError("graphs need a GPU")
+        self.model, self.opt, self.sink, self.warmup = model, opt, sink, warmup
+        self.graphs = {}
+
+    _in_line = GraphedTrainStep._in_line
+
+    def set_sink(self, sink) -> None:
+        if sink is not self.sink:
+            self.sink = sink
+            self.graphs.clear()
+
+    def replays(self) -> bool:
+        """False for a model whose forward sizes tensors on the host from the batch's contents (the coarse co-attention family)."""
+        return not type(getattr(self.model, "attn", None)).__module__.endswith(".coarse")
+
+    def _body(self, static, lossfun, representations):
+        with torch.no_grad(), self._in_line():
+            static.reset_derived()
+            static.emit()
+            y, (g1, g2) = self.opt.functional_predict(static.pb)
+            loss = None if lossfun is None else lossfun(y, static.t)
+            if representations and (g1 is None or g2 is None):
+                raise ValueError("representations: the model leaves no g1 / g2")
+            if self.sink is not None:
+                self.sink.launch(y, static.t, loss, g1 if representations else None, g2 if representations else None)
+            return y, loss, g1, g2
+
+    def __call__(self, static, lossfun=None, representations: bool = False) -> torch.Tensor:
+        if not callable(getattr(static, "emit", None)):
+            raise ValueError("GraphedPredict runs on a StaticPairBatch (PairBatches(layout='static'))")
+        sink = self.sink
+        if sink is not None:
+            sink.reserve(len(static.t), lossfun is not None)        # the host's capacity check, before any launch
+        was_training = self.model.training
+        if was_training:                                             # (an evaluation loop has done it: no walk over the modules then)
+            self.model.eval()
+        try:
+            if not self.replays():
+                return self._body(static, lossfun, representations)[0]
+            lf = (getattr(lossfun, "__func__", lossfun), id(getattr(lossfun, "__self__", None)))
+            key = (id(static.pb), id(static.t), lf, bool(representations))
+            if key not in self.graphs:
+                words = None if sink is None else sink.words.clone()
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(self.warmup):
+                        self._body(static, lossfun, representations)
+                torch.cuda.current_stream().wait_stream(s)
+                if words is not None:
+                    sink.words.copy_(words)              # the warm-up's appends never happened
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    outs = self._body(static, lossfun, representations)
+                self.graphs[key] = (g, outs, static.pb, static.t, lossfun)
+            g, outs = self.graphs[key][:2]
+            g.replay()
+            return outs[0]
+        finally:
+            if was_training:
+                self.model.train(True)

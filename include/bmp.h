@@ -795,6 +795,21 @@ int bmp_adam_step_hooked(float* p, const float* g, float* m, float* v, int n, fl
                          float l2_rate, float l1_rate, const float* hook_dev, int hook_order, const float* partials,
                          float* norm_out, bmp_stream_t stream);
 
+/* ---- evaluation scores kept on the device (training/extensions/batch_evaluator.py:49-100 gathers every batch's logits on the
+ * host; eval_coattention.py:103-124 also the two molecule vectors) ----
+ * bmp_eval_append: one batch's rows go behind the rows of the batches before it, at a cursor held in DEVICE memory, so that a
+ * launch recorded in a HIP graph lands behind the previous replay.  src / width / dst: HOST arrays of 4 -- up to four float row
+ * blocks [B x width[k]] (src[k] NULL or width[k] 0: absent); the pointers and widths travel in the kernel arguments.  Block k is
+ * copied to dst[k] + cursor[0] * width[k] (dst[k]: cap_rows rows), the int32 labels lab [B x lab_width] (may be NULL) to lab_dst
+ * likewise, loss[0] (device scalar, may be NULL) to loss_slots[cursor[1]] (cap_batches slots); then cursor[0] += B, cursor[1] += 1.
+ * A batch that does not fit (cursor[0] + B > cap_rows or cursor[1] + 1 > cap_batches) sets overflow[0] = 1, writes nothing else
+ * and leaves the cursor alone.  16-byte copies for a block with width % 4 == 0 whose source and destination are 16-byte aligned
+ * at this cursor, dwords otherwise (sources and destinations need 4-byte alignment only).  Two launches on `stream`: the copy,
+ * then the advance.  Start of a set: zero the two cursor words and the overflow word (hipMemsetAsync / tensor.zero_()). */
+int bmp_eval_append(const float* const* src, const int* width, const int* lab, int lab_width, const float* loss, int B,
+                    float* const* dst, int* lab_dst, float* loss_slots, int* cursor, int cap_rows, int cap_batches,
+                    int* overflow, bmp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
