@@ -189,6 +189,19 @@ __global__ __launch_bounds__(512) void k_ggnn_step_fwd(StepArgs a) {
     step(std::integral_constant<bool, FIRST>{}, a.WT, a.bE, a.AT, a.b, a.m, a.rz, a.c, a.hout);
 }
 
+// a * b + c in one rounding (FUSE) or two.  The step backward's `ex += d(r*h) r` is written with it: the compiler's contraction
+// has always fused that line in the tile-table instances and not in the whole-tile ones, and which it picks moves with the
+// code around the line; pinned per instance, dh stays bit for bit what each of them has written so far.
+template <bool FUSE>
+__device__ __forceinline__ f32x4 fz_mul_add(f32x4 a, f32x4 b, f32x4 c) {
+    if constexpr (FUSE) return __builtin_elementwise_fma(a, b, c);
+    else {
+#pragma clang fp contract(off)
+        const f32x4 p = a * b;
+        return p + c;
+    }
+}
+
 // Backward of one step for one tile: all of the backward-data path (gate derivatives, the three
 // transposed gate GEMMs, the message-linear transpose and the transposed neighbour gather), and the
 // per-row pre-activation gradients [G | da] the weight-gradient GEMMs consume.
@@ -252,6 +265,14 @@ __global__ __launch_bounds__(512) void k_ggnn_step_bwd(StepArgs a) {
     }
 
     // ---- da_c = dh' z (1 - c^2) -> X ; da_z = dh' (c - h) z (1 - z) -> Y ; ex = dh' (1 - z): the direct part of dh ----
+    // ex (later calls only) is complete after the da_r block (+= d(r*h) r) and is read once, in the kernel's last line.  In
+    // between it is PARKED in the dh rows it will be added to instead of sitting in 32 registers through the gate products
+    // and the message backward: every thread stores its slots there (b_dh) and loads the same 16-byte pieces back ahead of the
+    // last group sync.  Only the wave's own store-then-load order on one address is involved, and the sum is the same two
+    // floats in the same order.  dh and dhout are distinct buffers in every caller (bmp/functional.py allocates dh per call);
+    // as one buffer they would do as well: a thread reads its dhout pieces in the prologue, before it writes the same pieces
+    // of dh, and no other thread touches them.  The fixed-stride clear above writes rows past nrows only, which no live slot
+    // stores or reloads.
     f32x4 ex[NV];
     {
         const f32x4 one = (f32x4){1.f, 1.f, 1.f, 1.f};
@@ -268,7 +289,7 @@ __global__ __launch_bounds__(512) void k_ggnn_step_bwd(StepArgs a) {
             const f32x4 gz = g4[v] * z4[v];
             const f32x4 dac = gz * (one - c4[v] * c4[v]);
             f32x4 dz = gz * (one - z4[v]);
-            if (first) { dz *= c4[v]; ex[v] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+            if (first) dz *= c4[v];          // (h = 0, no r gate: dh has no direct part)
             else { dz *= (c4[v] - h4[v]); ex[v] = g4[v] - gz; }
             RM_LDS(Xs, v) = dac;
             RM_LDS(Ys, v) = dz;
@@ -283,8 +304,18 @@ __global__ __launch_bounds__(512) void k_ggnn_step_bwd(StepArgs a) {
     const float* const Ar_h = a.A + (size_t)(4 * hi) * 2 * D + 4 * col;
     const int ld2[2] = {2 * D, 2 * D};
     const float* const Bc[2] = {Ac_h, Ac_h + 4 * D};
-    BPre<2> pre_c;
+    const float* const Bz[2] = {Az_h, Az_h + 4 * D};
+    const float* const Br[2] = {Ar_h, Ar_h + 4 * D};
+    const float* const Bu[1] = {a.Uc + (size_t)(4 * hi) * D + 4 * col};
+    const int ldu[1] = {D};
+    // The first B fragments of a product are requested ahead of the barrier, epilogue or product that precedes it
+    // (tile_b_prefetch), so that its MFMA loop does not open with an L2 round trip.  The da_z product of a later call is the
+    // one left cold: with its fragments in flight too the whole-tile instance spills, and it paid least of the three.
+    BPre<2> pre_c, pre_r, pre_z;
+    BPre<1> pre_u;
     tile_b_prefetch<2>(pre_c, Bc, ld2, D, rot);
+    if (first) tile_b_prefetch<2>(pre_z, Bz, ld2, D, rot);     // (first call: the da_z product follows the da_c product at once)
+    else tile_b_prefetch<1>(pre_u, Bu, ldu, D, rot);
     __syncthreads();                         // whole workgroup: the staged CSR and the counters are visible
     // The half's rows by (rare bond type, row): every MFMA of this kernel takes its A rows in that order (aoff), so all the
     // accumulators line up with the message backward's, where the order pays; what leaves an accumulator for a row-indexed
@@ -298,20 +329,22 @@ __global__ __launch_bounds__(512) void k_ggnn_step_bwd(StepArgs a) {
 
     f32x16 acc_x[2][RB];                     // [0] = dh, [1] = dm
     zero_acc(acc_x[0]); zero_acc(acc_x[1]);
-    tile_mma_n<VAR, 2, RB>(nrb, acc_x, Xw, LD, Bc, ld2, D, rot, &pre_c, aoff); // [dh | dm] += da_c . A_c
+    tile_mma_n<VAR, 2, RB>(nrb, acc_x, Xw, LD, Bc, ld2, D, fz_opaque(rot), &pre_c, aoff); // [dh | dm] += da_c . A_c
     if (!first) {
         f32x16 acc_d[1][RB];                 // d(r*h) = da_c . U
         zero_acc(acc_d[0]);
-        {
-            const float* const Bu[1] = {a.Uc + (size_t)(4 * hi) * D + 4 * col};
-            const int ldu[1] = {D};
-            tile_mma_n<VAR, 1, RB>(nrb, acc_d, Xw, LD, Bu, ldu, D, rot, nullptr, aoff);
-        }
+        // r comes from HBM for the first time here (the prologue took the z half of the rows): requested ahead of the U
+        // product it arrives under 128 MFMAs per wave; behind it, the da_r block waited for it with both groups of a SIMD
+        // idle (measured: 7 us of a 224 us launch).  h was read by the prologue and answers from L2 under the group barrier.
+        f32x4 r4[NV], h4[NV];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) if (RM_LIVE(v)) r4[v] = rm_ld<D, 2 * D>(b_rz, v);
+        tile_mma_n<VAR, 1, RB>(nrb, acc_d, Xw, LD, Bu, ldu, D, fz_opaque(rot), &pre_u, aoff);
         FZ_GSYNC();                          // all waves of this half done with da_c in X
         FZ_FOR_ACC { Xs[FZ_ROWOF(rb, reg) * LD + col] = acc_d[0][rb][reg]; }
-        f32x4 r4[NV], h4[NV];                // in flight across the group barrier
 #pragma unroll
-        for (int v = 0; v < NV; ++v) if (RM_LIVE(v)) { r4[v] = rm_ld<D, 2 * D>(b_rz, v); h4[v] = rm_ld<D, D>(b_h, v); }
+        for (int v = 0; v < NV; ++v) if (RM_LIVE(v)) h4[v] = rm_ld<D, D>(b_h, v);
+        tile_b_prefetch<2>(pre_r, Br, ld2, D, rot);
         FZ_GSYNC();
         // da_r = d(r*h) h r (1-r) -> X (in place) ; ex += d(r*h) r
 #pragma unroll
@@ -319,20 +352,16 @@ __global__ __launch_bounds__(512) void k_ggnn_step_bwd(StepArgs a) {
             const f32x4 drh = RM_LDS(Xs, v);
             const f32x4 dr = drh * r4[v];
             const f32x4 dar = dr * h4[v] * ((f32x4){1.f, 1.f, 1.f, 1.f} - r4[v]);
-            ex[v] += dr;
+            ex[v] = fz_mul_add<VAR>(drh, r4[v], ex[v]);
             RM_LDS(Xs, v) = dar;
             rm_st<D, 7 * D>(b_o, v, dar, 4 * D);
+            rm_st<D, D>(b_dh, v, ex[v]);     // parked (see the head of the kernel): ex leaves the register file here
         }
         FZ_GSYNC();
-        {
-            const float* const Br[2] = {Ar_h, Ar_h + 4 * D};
-            tile_mma_n<VAR, 2, RB>(nrb, acc_x, Xw, LD, Br, ld2, D, rot, nullptr, aoff);
-        }
+        tile_mma_n<VAR, 2, RB>(nrb, acc_x, Xw, LD, Br, ld2, D, fz_opaque(rot), &pre_r, aoff);
     }
-    {   // da_z has been waiting in Y since the prologue
-        const float* const Bz[2] = {Az_h, Az_h + 4 * D};
-        tile_mma_n<VAR, 2, RB>(nrb, acc_x, Yw, LD, Bz, ld2, D, rot, nullptr, aoff);
-    }
+    // da_z has been waiting in Y since the prologue
+    tile_mma_n<VAR, 2, RB>(nrb, acc_x, Yw, LD, Bz, ld2, D, fz_opaque(rot), first ? &pre_z : nullptr, aoff);
     FZ_GSYNC();                              // all waves of this half done with X and Y
     // ---- X <- dm ----
     FZ_FOR_ACC { Xs[FZ_ROWOF(rb, reg) * LD + col] = acc_x[1][rb][reg]; }
@@ -362,11 +391,19 @@ __global__ __launch_bounds__(512) void k_ggnn_step_bwd(StepArgs a) {
         if (any) tile_mma_msg<VAR, 1, RB>(nrb, e, ro.nbr, bi, acc_h, Yw, LD, Bp, ldw, D, rot, &pre);
         FZ_GSYNC();
     }
-    // ---- dh = (MFMA part, via Y: accumulator position -> row) + ex ----
+    // ---- dh = (MFMA part, via Y: accumulator position -> row) + ex, which comes back from the dh rows under the group sync ----
+    f32x4 pk[NV];
+    if (!first) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) if (RM_LIVE(v)) pk[v] = rm_ld<D, D>(b_dh, v);
+    }
     FZ_FOR_ACC { Ys[FZ_ROWOF(rb, reg) * LD + col] = acc_h[0][rb][reg]; }
     FZ_GSYNC();
 #pragma unroll
-    for (int v = 0; v < NV; ++v) if (RM_LIVE(v)) rm_st<D, D>(b_dh, v, RM_LDS(Ys, v) + ex[v]);
+    for (int v = 0; v < NV; ++v) if (RM_LIVE(v)) {
+        if (first) rm_st<D, D>(b_dh, v, RM_LDS(Ys, v));
+        else rm_st<D, D>(b_dh, v, RM_LDS(Ys, v) + pk[v]);
+    }
 #undef RM_LIVE
 #undef RM_ROW
 #undef RM_C4

@@ -130,6 +130,12 @@ __device__ __forceinline__ void tile_mma_n(int nrb, f32x16 (&acc)[NB][RB], const
     }
 }
 
+// An opaque copy of a wave-uniform int.  A kernel that runs several products over the SAME LDS tile hands each of them its
+// own copy of `rot`: the unrolled loop's per-k-step A addresses (tile + aoff + 4 k, one VGPR each) are then temporaries of
+// that product.  With one `rot` for all the compiler keeps the 16 * RB addresses of the first product for the next ones,
+// across every phase in between.
+__device__ __forceinline__ int fz_opaque(int x) { asm volatile("" : "+s"(x)); return x; }
+
 template <int N>
 __device__ __forceinline__ void zero_acc(f32x16 (&acc)[N]) {
 #pragma unroll
